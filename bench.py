@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: query placements/sec on the 10k-leaf tree, 150 bp reads.
 
-    python bench.py --gpus N --steps K --warmup W [--config C3]
+    python bench.py --gpus N --steps K --warmup W [--config C3] [--dump-outputs DIR]
 
 A "step" is one pass of the placement hot path (`cls_place_batch_device`, the
 C-ABI entry a Rust caller would bind) over one batch of synthetic reads that is
@@ -35,6 +35,26 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_FIELDS = ("status", "one", "rest", "levels", "clade_id")
+DUMP_CAP_BYTES = 64 * 10**6  # --dump-outputs writes at most this much, .npy headers included
+
+
+def dump_outputs(out_dir, recs):
+    """--dump-outputs: the placement records the timed path returned, one float64 DIR/<field>.npy per record field
+    and DIR/read.npy, the position of each row in the read stream.  Beyond DUMP_CAP_BYTES the rows are a fixed
+    sample (seed 0) in stream order, so two builds run with the same arguments can be compared row for row.
+    Returns the number of rows written."""
+    n = len(recs)
+    per_row = 8 * (len(DUMP_FIELDS) + 1)
+    cap = (DUMP_CAP_BYTES - 4096) // per_row  # (4 KiB for the six .npy headers)
+    rows = np.arange(n) if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+    cols = {f: recs[f][rows] for f in DUMP_FIELDS}
+    assert (cols["clade_id"] < 2**53).all(), "clade ids beyond 2^53 do not survive float64"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "read.npy"), rows.astype(np.float64))
+    for f, col in cols.items():
+        np.save(os.path.join(out_dir, f + ".npy"), col.astype(np.float64))
+    return len(rows)
 
 
 def survey_model_bytes(read_lens, stats):
@@ -229,7 +249,12 @@ def main():
     ap.add_argument("--no-host-window", action="store_true")
     ap.add_argument("--dump-records", default="", help="rank 0 writes the records it holds after the last step (all ranks' "
                     "shards in rank order at N > 1) to this .npy file: lets a test check the gathered records against the oracle")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes the records of the last timed step (all "
+                    "ranks' at N > 1) to DIR/<field>.npy as float64, at most 64 MB (a fixed sample of the reads beyond): "
+                    "lets two builds be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -477,7 +502,7 @@ def main():
             line["roofline"]["random_line_rate"] = {"achieved_glines_per_s": lines, "peak_glines_per_s": peak_lines,
                                                     "frac": (lines / peak_lines) if lines else None,
                                                     "what": gref["what"]}
-        if args.dump_records:
+        if args.dump_records or args.dump_outputs:
             last = (args.steps - 1) & 1
             if world == 1:
                 allrec = now.copy()
@@ -487,8 +512,11 @@ def main():
                 allrec = np.concatenate([x.cpu().numpy() for x in gathered[last]]).view(_abi.PLACEMENT_DTYPE)
             if strong:  # drop the zero tail of a short last shard
                 allrec = allrec[:total_reads]
-            np.save(args.dump_records, allrec)
-            line["config"]["dumped_records"] = int(len(allrec))
+            if args.dump_records:
+                np.save(args.dump_records, allrec)
+                line["config"]["dumped_records"] = int(len(allrec))
+            if args.dump_outputs:
+                line["config"]["dumped_outputs"] = {"rows": dump_outputs(args.dump_outputs, allrec), "of": int(len(allrec))}
         if not args.no_host_window and world == 1 and mine:
             hw, host_recs = host_window(db, bases, offsets, mine)
             for f in ("status", "one", "rest", "levels", "clade_id"):
