@@ -164,3 +164,146 @@ def test_leaves_only_oracle_equals_explicit_oracle(case):
                 assert (got[f] == want[f]).all(), (f, kw)
             for f in ("n_query_kmers", "n_matched", "n_with_root", "leaf_postings"):
                 assert (gst[f] == wst[f]).all(), (f, kw)
+
+
+# ---- foreign buckets: entries filed under a bucket that is not their own prefix's --------------------------------------
+# kmers_map.rs:279-297 keeps a hit if its bucket's key is the minimizer of SOME query k-mer (either strand, k-mer start
+# positions only), not necessarily the hit's own.  The GPU tests (tests/test_gpu_foreign_buckets.py) hold the kernels to
+# the C port on such indexes; these pin the C port to the literal restatement there.
+
+def _node_sets_by_hash(flat):
+    off = flat.kmer_node_off.astype(np.int64)
+    return {int(h): sorted(flat.node_ids[off[j]:off[j + 1]].tolist()) for j, h in enumerate(flat.kmer_hash)}
+
+
+def test_refile_helpers_keep_every_entry():
+    from tests.helpers import drop_kmers, foreign_refile, kmer_bucket_index, kmers_inside_clade, clade_with_leaves, split_buckets
+
+    s = SynthDb(30, 300, 12, 7)
+    flat = s.flat
+    move = kmers_inside_clade(flat, clade_with_leaves(flat, 5, 10)) & (np.random.default_rng(1).random(flat.n_kmers) < 0.3)
+    g, moved = foreign_refile(flat, move, seed=2)
+    assert moved.sum() > 100 and not (moved & ~move).any()
+    assert _node_sets_by_hash(g) == _node_sets_by_hash(flat) and len(np.unique(g.kmer_hash)) == g.n_kmers
+    key_of = dict(zip(g.kmer_hash.tolist(), g.bucket_key[kmer_bucket_index(g)].tolist()))
+    own = flat.bucket_key[kmer_bucket_index(flat)]
+    assert all(key_of[int(h)] != int(k) for h, k in zip(flat.kmer_hash[moved], own[moved]))
+    assert all(key_of[int(h)] == int(k) for h, k in zip(flat.kmer_hash[~moved], own[~moved]))
+    assert len(np.unique(g.bucket_key)) == len(g.bucket_key)
+    d = drop_kmers(flat, moved)
+    assert d.n_kmers == flat.n_kmers - moved.sum() and not np.isin(d.kmer_hash, flat.kmer_hash[moved]).any()
+    sp = split_buckets(flat, 20, seed=3)
+    assert len(sp.bucket_key) == len(flat.bucket_key) + 20 and _node_sets_by_hash(sp) == _node_sets_by_hash(flat)
+    lo = foreign_refile(flat.to_leaves_only(), move, seed=2)[0]
+    assert lo.leaves_only and _node_sets_by_hash(lo.to_explicit()) == _node_sets_by_hash(g)
+
+
+def _foreign_index(k, m, variant, n_leaves=30, ref_len=300, seed=2):
+    """A small SynthDb index with ~30 % of the k-mers of one clade refiled under foreign keys."""
+    from tests.helpers import clade_with_leaves, foreign_refile, kmers_inside_clade, split_buckets
+
+    s = SynthDb(n_leaves, ref_len, k, m)
+    flat = split_buckets(s.flat, 40, seed=seed) if variant == "dup" else s.flat
+    move = kmers_inside_clade(flat, clade_with_leaves(flat, n_leaves // 6, n_leaves // 2)) & (np.random.default_rng(seed).random(flat.n_kmers) < 0.3)
+    refiled, moved = foreign_refile(flat, move, seed=seed, unhashed_frac=1.0 if variant == "unhashed" else 0.3)
+    if variant == "leaves":
+        refiled = foreign_refile(flat.to_leaves_only(), move, seed=seed, unhashed_frac=0.3)[0]
+    return s, flat, refiled, moved
+
+
+@pytest.mark.parametrize("k,m,variant", [(10, 0, "mixed"), (12, 4, "mixed"), (12, 7, "mixed"), (12, 8, "dup"), (12, 10, "mixed"),
+                                         (10, 11, "mixed"), (12, 7, "unhashed"), (17, 10, "dup"), (12, 7, "leaves")])
+def test_port_matches_literal_on_foreign_buckets(k, m, variant):
+    """m = 0 (one key, 0: a foreign key is never any query's minimizer), m <= 8 and 9..k (the two regimes of the kernels'
+    bucket table), m > k (the minimizer is the whole k-mer's hash: a foreign key is another k-mer's), keys no m-string
+    hashes to, duplicate bucket keys, a leaves-only input.  Records, and |M| against the literal trace."""
+    s, flat, refiled, moved = _foreign_index(k, m, variant)
+    explicit = refiled.to_explicit() if refiled.leaves_only else refiled
+    tree = op.flat_to_literal(explicit)
+    port = op.OraclePort(refiled)
+    bases, offsets, _ = s.reads(300, 150, frac_random=0.05, err=0.02)
+    for kw in (dict(), dict(remove_intersection=True), dict(min_match_coverage=1.0)):
+        want = op.literal_place_batch(tree, bases, offsets, **kw)
+        got, st = port.place_batch(bases, offsets, op.make_params(**kw), threads=2, want_stats=True)
+        assert len(records_equal(got, want)) == 0, kw
+    raw = bytes(bases)
+    for i in range(0, 300, 5):
+        tr = lit.Trace()
+        try:
+            lit.place_sequence(f"r{i}", raw[int(offsets[i]):int(offsets[i + 1])].decode(), tree, trace=tr)
+        except (lit.PlaceError, ValueError):
+            continue
+        assert (tr.n_query_kmers, tr.query_kmers_len) == (st[i]["n_query_kmers"], st[i]["n_matched"])
+    # the input is discriminating: the refiled entries change |M| against leaving them in their own bucket
+    own = op.OraclePort(flat).place_batch(bases, offsets, threads=2, want_stats=True)[1]
+    assert (own["n_matched"] != st["n_matched"]).mean() > 0.05
+
+
+def _revcomp(s: str) -> str:
+    return s[::-1].translate(str.maketrans("ACGT", "TGCA"))
+
+
+def _starts(seq: str, k: int, m: int) -> set:
+    """The m-prefixes of the k-mers of both strands: the query's minimizers, as strings."""
+    rc = _revcomp(seq)
+    return {x[i:i + m] for x in (seq, rc) for i in range(len(seq) - k + 1)}
+
+
+@pytest.mark.parametrize("layout,accepted", [("rc_strand", True), ("last_k_minus_1", False), ("at_L_minus_k", True)])
+def test_foreign_key_found_among_the_query_minimizers(layout, accepted):
+    """Crafted reads for ONE refiled k-mer X, filed under the key of an m-string P that is not X's prefix: P is the prefix
+    of a k-mer of the reverse-complement strand only (accepted); P lies inside the last k-1 bases, where no k-mer starts
+    (rejected); P starts at L-k (accepted).  The read's property is checked by string search; |M| must be the own-bucket
+    index's (accepted) or one less (rejected)."""
+    from tests.helpers import refile_kmers
+
+    k, m = 10, 5
+    s = SynthDb(30, 300, k, m)
+    flat = s.flat
+    leaf = s.leaf_seq(3)
+    X = leaf[100:100 + k]
+    hx = lit.hash_kmer(X)
+    j = int(np.nonzero(flat.kmer_hash == np.uint64(hx))[0][0])
+    rng = np.random.default_rng(7)
+    P = "".join("ACGT"[c] for c in rng.integers(0, 4, m))
+    while P == X[:m] or P in leaf or _revcomp(P) in leaf:
+        P = "".join("ACGT"[c] for c in rng.integers(0, 4, m))
+    move = np.zeros(flat.n_kmers, dtype=bool)
+    move[j] = True
+    target = np.zeros(flat.n_kmers, dtype=np.uint64)
+    target[j] = lit.hash_kmer(P)
+    refiled = refile_kmers(flat, move, target)
+    for attempt in range(200):
+        r = np.random.default_rng(100 + attempt)
+        fill = "".join("ACGT"[c] for c in r.integers(0, 4, 30))
+        if layout == "rc_strand":
+            read = X + fill + _revcomp(P)  # P starts the reverse complement's first k-mer
+        elif layout == "last_k_minus_1":
+            read = X + fill + P + fill[:k - 1 - m]  # P ends the read, inside the last k-1 bases
+        else:
+            read = X + fill + P + fill[:k - m]  # P starts the last forward k-mer
+        L = len(read)
+        fwd = {read[i:i + m] for i in range(L - k + 1)}
+        rcs = {_revcomp(read)[i:i + m] for i in range(L - k + 1)}
+        if read.count(X) != 1 or X in _revcomp(read):
+            continue
+        if layout == "rc_strand" and P in rcs and P not in fwd:
+            break
+        if layout == "last_k_minus_1" and P not in fwd | rcs and P in read[L - k + 1:]:
+            break
+        if layout == "at_L_minus_k" and [i for i in range(L - k + 1) if read[i:i + m] == P] == [L - k] and P not in rcs:
+            break
+    else:
+        raise AssertionError("no read with the intended property")
+    assert (P in _starts(read, k, m)) == accepted
+    bases = np.frombuffer(read.encode(), dtype=np.uint8)
+    offsets = np.array([0, L], dtype=np.uint64)
+    n = {}
+    for tag, f in (("refiled", refiled), ("own", flat)):
+        tr = lit.Trace()
+        lit.place_sequence("q", read, op.flat_to_literal(f), trace=tr)
+        got, st = op.OraclePort(f).place_batch(bases, offsets, want_stats=True)
+        assert len(records_equal(got, op.literal_place_batch(op.flat_to_literal(f), bases, offsets))) == 0
+        assert st[0]["n_matched"] == tr.query_kmers_len
+        n[tag] = tr.query_kmers_len
+    assert n["refiled"] == (n["own"] if accepted else n["own"] - 1)
