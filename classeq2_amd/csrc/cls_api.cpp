@@ -488,8 +488,7 @@ extern "C" int cls_db_kernel_name(const cls_db* db, char* buf, size_t len) {
         { std::lock_guard<std::mutex> g(const_cast<cls_db*>(db)->ws_mu); max_len = db->max_read_len; }
         // (as cls_place_batch_device would plan a launch: long reads only when the caller opted in)
         const cls::PlacePlan plan = cls::plan_place(db->dev, 4096, (uint32_t)db->n_cu, false, (uint32_t)(2 * max_len), max_len ? 4096 : 0);
-        const std::string s = cls::dominant_kernel_name(db->dev, false, &plan);
-        snprintf(buf, len, "%s", s.c_str());
+        snprintf(buf, len, "%s", plan.timed_name.c_str());
         return CLS_OK;
     } catch (...) {
         return fail(CLS_E_INTERNAL, "cls_db_kernel_name: unknown exception");

@@ -2398,59 +2398,98 @@ size_t smem_of(const DbDev& db, int c) {
            (child_in_lds(db) ? (size_t)WAVES_PER_BLOCK * 2 * child_ws_stride(db) * 4 : 0);
 }
 
+// The kernel of a wave-per-read class: fast path, split-tree or generic (one of the three pointers is set)
+using FastFn = decltype(place_fast_kernel<CLS_SLOTS[0], CLS_SET_BITS[0], false, false, 0, false>);
+using SplitFn = decltype(place_split_kernel<CLS_SLOTS[0], CLS_SET_BITS[0], false, false>);
+using WaveFn = decltype(place_wave_kernel<CLS_SLOTS[0], CLS_SET_BITS[0], false, false>);
+struct ClassKernel {
+    FastFn* fast;
+    SplitFn* split;
+    WaveFn* wave;
+    size_t smem;
+    std::string name;
+    const void* fn() const { return fast ? (const void*)fast : split ? (const void*)split : (const void*)wave; }
+};
 template <int SLOTS, int SET_BITS>
-const void* kernel_of_t(const DbDev& db, bool stats) {
-    if (use_fast(db)) {
-#define CLS_FAST_OF(A32, MD, PO) (stats ? (const void*)place_fast_kernel<SLOTS, SET_BITS, true, A32, MD, PO> : (const void*)place_fast_kernel<SLOTS, SET_BITS, false, A32, MD, PO>)
-#define CLS_FAST_OF2(A32, MD) (db.binary_tree ? CLS_FAST_OF(A32, MD, false) : CLS_FAST_OF(A32, MD, true))
-        const int mode = fast_mode(db);
-        if (mode == 2) return CLS_FAST_OF2(true, 2);  // (the hashed front is only instantiated with 32-bit offsets: use_fast)
-        if (mode == 3) return CLS_FAST_OF2(true, 3);  // (the 16-byte table only exists for k <= 12: 32-bit offsets)
-        if (mode == 4) return CLS_FAST_OF2(true, 4);
-        if (db.addr32) return mode == 1 ? CLS_FAST_OF2(true, 1) : CLS_FAST_OF2(true, 0);
-        return mode == 1 ? CLS_FAST_OF2(false, 1) : CLS_FAST_OF2(false, 0);
-#undef CLS_FAST_OF2
-#undef CLS_FAST_OF
-    }
-    if (db.format == FMT_SPLIT) {
-        if (db.binary_tree) return stats ? (const void*)place_split_kernel<SLOTS, SET_BITS, true, false> : (const void*)place_split_kernel<SLOTS, SET_BITS, false, false>;
-        return stats ? (const void*)place_split_kernel<SLOTS, SET_BITS, true, true> : (const void*)place_split_kernel<SLOTS, SET_BITS, false, true>;
-    }
-    const bool binary = db.max_nonleaf_arity <= 2;  // no node has more than two non-LEAF children
-    if (stats) return binary ? (const void*)place_wave_kernel<SLOTS, SET_BITS, true, true> : (const void*)place_wave_kernel<SLOTS, SET_BITS, true, false>;
-    return binary ? (const void*)place_wave_kernel<SLOTS, SET_BITS, false, true> : (const void*)place_wave_kernel<SLOTS, SET_BITS, false, false>;
+ClassKernel class_kernel_t(const DbDev& db, int c, bool stats) {
+    const size_t smem = smem_of(db, c);
+    auto fast = [&](auto... v) { return ClassKernel{place_fast_kernel<decltype(v)::value...>, nullptr, nullptr, smem, instance_name("place_fast_kernel", v...)}; };
+    auto split = [&](auto... v) { return ClassKernel{nullptr, place_split_kernel<decltype(v)::value...>, nullptr, smem, instance_name("place_split_kernel", v...)}; };
+    auto wave = [&](auto... v) { return ClassKernel{nullptr, nullptr, place_wave_kernel<decltype(v)::value...>, smem, instance_name("place_wave_kernel", v...)}; };
+    const Int<SLOTS> sl;
+    const Int<SET_BITS> sb;
+    return with_bool(stats, [&](auto st) {
+        if (use_fast(db)) {
+            return with_bool(!db.binary_tree, [&](auto poly) {
+                const std::true_type addr32;  // (the hashed front and the 16-byte table (k <= 12) only exist with 32-bit offsets)
+                switch (fast_mode(db)) {
+                    case 2: return fast(sl, sb, st, addr32, Int<2>{}, poly);
+                    case 3: return fast(sl, sb, st, addr32, Int<3>{}, poly);
+                    case 4: return fast(sl, sb, st, addr32, Int<4>{}, poly);
+                }
+                return with_bool(db.addr32, [&](auto a32) { return fast_mode(db) == 1 ? fast(sl, sb, st, a32, Int<1>{}, poly) : fast(sl, sb, st, a32, Int<0>{}, poly); });
+            });
+        }
+        if (db.format == FMT_SPLIT) return with_bool(!db.binary_tree, [&](auto poly) { return split(sl, sb, st, poly); });
+        return with_bool(db.max_nonleaf_arity <= 2, [&](auto binary) { return wave(sl, sb, st, binary); });  // (no node has more than two non-LEAF children)
+    });
 }
-const void* kernel_of(const DbDev& db, int c, bool stats) {
-    if (c == 0 && set_bits_of(db, 0) != CLS_SET_BITS[0]) return kernel_of_t<CLS_SLOTS[0], NARROW_CANON_BITS>(db, stats);
-    return c == 0 ? kernel_of_t<CLS_SLOTS[0], CLS_SET_BITS[0]>(db, stats) : kernel_of_t<CLS_SLOTS[1], CLS_SET_BITS[1]>(db, stats);
+ClassKernel class_kernel(const DbDev& db, int c, bool stats) {
+    if (c == 1) return class_kernel_t<CLS_SLOTS[1], CLS_SET_BITS[1]>(db, 1, stats);
+    if (set_bits_of(db, 0) != CLS_SET_BITS[0]) return class_kernel_t<CLS_SLOTS[0], NARROW_CANON_BITS>(db, 0, stats);  // (a -DCLS_NARROW_CANON_BITS build)
+    return class_kernel_t<CLS_SLOTS[0], CLS_SET_BITS[0]>(db, 0, stats);
 }
 
-uint32_t blk_seq_cap(const DbDev& db) { return (2 * (64 * BLK_WAVES * BLK_SLOTS / 2 + db.k) + 15) & ~15u; }
-size_t blk_smem(const DbDev& db);
 uint32_t child_ws_stride(const DbDev& db) {
     if (db.format == FMT_SPLIT) return db.binary_tree ? 0u : ((std::max(db.max_nonleaf_arity, 1u) + 63) & ~63u);
     return db.max_nonleaf_arity <= 2 ? 0u : ((db.max_nonleaf_arity + 63) & ~63u);
 }
-size_t blk_smem(const DbDev& db) {
-    return (size_t)blk_seq_cap(db) + (4u << BLK_SET_BITS) + 4u * 64 * BLK_WAVES * BLK_SLOTS + 64 +
-           (child_in_lds(db) ? (size_t)2 * child_ws_stride(db) * 4 : 0);
+uint32_t blk_seq_cap(const DbDev& db) { return (2 * (64 * BLK_WAVES * BLK_SLOTS / 2 + db.k) + 15) & ~15u; }
+auto block_kernel(const DbDev& db, bool stats) {
+    const size_t smem = (size_t)blk_seq_cap(db) + (4u << BLK_SET_BITS) + 4u * 64 * BLK_WAVES * BLK_SLOTS + 64 +
+                        (child_in_lds(db) ? (size_t)2 * child_ws_stride(db) * 4 : 0);
+    auto inst = [&](auto... v) { return pick(place_block_kernel<decltype(v)::value...>, smem, "place_block_kernel", v...); };
+    const bool split = db.format == FMT_SPLIT, binary = split ? db.binary_tree != 0 : db.max_nonleaf_arity <= 2;
+    return with_bool(stats, [&](auto st) { return with_bool(binary, [&](auto bi) { return with_bool(split, [&](auto sp) {
+        return inst(Int<BLK_WAVES>{}, Int<BLK_SLOTS>{}, Int<BLK_SET_BITS>{}, st, bi, sp);
+    }); }); });
+}
+auto long_kernel(const DbDev& db, bool stats) {
+    auto inst = [&](auto... v) { return pick(place_long_kernel<decltype(v)::value...>, 0, "place_long_kernel", v...); };
+    return with_bool(db.format == FMT_SPLIT, [&](auto sp) { return with_bool(stats, [&](auto st) { return inst(sp, st); }); });
+}
+
+// The locality-key kernel: the full one or, with the default knobs, the one that keys two reads per wavefront
+using KeyFn = decltype(order_key_kernel<2, true, true, false>);
+using KeyHalfFn = decltype(order_key_half_kernel<true>);
+struct KeyKernel {
+    KeyFn* full;
+    KeyHalfFn* half;
+    size_t smem;
+    std::string name;
+    const void* fn() const { return full ? (const void*)full : (const void*)half; }
+};
+// `sizing`: the instance plan.grid_key is sized by -- the full kernel over forward windows with its LDS, even where the half
+// kernel is launched with none (as it has been measured; changing it is a tuning question)
+KeyKernel key_kernel(const DbDev& db, bool sizing) {
+    const Tuning& tn = tuning();
+    const bool fwd = !tn.order_both_strands, hashed = fast_mode(db) == 2;
+    if (!sizing && !hashed && fwd && tn.order_windows == 64 && (uint32_t)tn.order_sample_shift >= 32)
+        return with_bool(db.addr32, [&](auto a32) { return KeyKernel{nullptr, order_key_half_kernel<decltype(a32)::value>, 0, instance_name("order_key_half_kernel", a32)}; });
+    const uint32_t ac = ascii_cap_of(db, 0);
+    const size_t smem = (size_t)WAVES_PER_BLOCK * (ac + (db.direct ? 4u * (((ac >> 4) + 2 + 3) & ~3u) : 0u) + 16u);
+    auto inst = [&](auto... v) { return KeyKernel{order_key_kernel<decltype(v)::value...>, nullptr, smem, instance_name("order_key_kernel", v...)}; };
+    auto of = [&](auto a32, auto hs) {
+        // (CLS_ORDER_WINDOWS windows make a read's key -- 64 = one lookup slot per lane, 160 = all of a 150 bp read; forward
+        // windows only, at most 64 of them: two slots, not the placement kernel's five)
+        if (fwd && tn.order_windows <= 64) return inst(Int<2>{}, a32, std::true_type{}, hs);
+        if (fwd || sizing) return inst(Int<CLS_SLOTS[0]>{}, a32, std::true_type{}, hs);
+        return inst(Int<CLS_SLOTS[0]>{}, a32, std::false_type{}, hs);
+    };
+    if (hashed) return of(std::true_type{}, std::true_type{});
+    return db.addr32 ? of(std::true_type{}, std::false_type{}) : of(std::false_type{}, std::false_type{});
 }
 }  // namespace
-
-std::string dominant_kernel_name(const DbDev& db, bool stats, const PlacePlan* plan) {
-    const std::string sl = std::to_string(CLS_SLOTS[0]) + ", " + std::to_string(set_bits_of(db, 0)) + ", " + (stats ? "true" : "false");
-    auto b = [](bool v) { return std::string(v ? "true" : "false"); };
-    if (plan && plan->time_tile) return tile_kernel_name(db, stats, plan->tile_name_threads);  // a launch provisioned for long reads (or a bench of gene-length reads): the LDS-tiled kernel is the one that is timed
-    if (tuning().time_class == 2) {
-        const std::string bl = std::to_string(BLK_WAVES) + ", " + std::to_string(BLK_SLOTS) + ", " + std::to_string(BLK_SET_BITS) + ", " + b(stats);
-        if (db.format == FMT_SPLIT) return "place_block_kernel<" + bl + ", " + b(db.binary_tree != 0) + ", true>";
-        return "place_block_kernel<" + bl + ", " + b(db.max_nonleaf_arity <= 2) + ", false>";
-    }
-    if (use_fast(db))
-        return "place_fast_kernel<" + sl + ", " + b(fast_mode(db) == 2 || db.addr32) + ", " + std::to_string(fast_mode(db)) + ", " + b(!db.binary_tree) + ">";
-    if (db.format == FMT_SPLIT) return "place_split_kernel<" + sl + ", " + b(!db.binary_tree) + ">";
-    return "place_wave_kernel<" + sl + ", " + b(db.max_nonleaf_arity <= 2) + ">";
-}
 
 PlacePlan plan_place(const DbDev& db, uint32_t n_reads, uint32_t n_cu, bool stats, uint32_t long_cap, uint32_t n_long) {
     PlacePlan p{};
@@ -2461,8 +2500,8 @@ PlacePlan plan_place(const DbDev& db, uint32_t n_reads, uint32_t n_cu, bool stat
     uint64_t child_words = 0;
     for (int c = 0; c < N_CLASSES; ++c) {
         int per_cu = forced;
-        if (per_cu <= 0 &&
-            (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_of(db, c, stats), 64 * WAVES_PER_BLOCK, smem_of(db, c)) != hipSuccess || per_cu <= 0))
+        const ClassKernel k = class_kernel(db, c, stats);
+        if (per_cu <= 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn(), 64 * WAVES_PER_BLOCK, k.smem) != hipSuccess || per_cu <= 0))
             per_cu = 1;
         uint32_t cap = n_cu * (uint32_t)per_cu;
         if (child_ws_stride(db) && !child_in_lds(db)) {  // bound the per-wave child-counter workspace to 128 MiB per class
@@ -2487,14 +2526,8 @@ PlacePlan plan_place(const DbDev& db, uint32_t n_reads, uint32_t n_cu, bool stat
         p.grid[1] = std::max<uint32_t>(8, p.grid[1] & ~7u);
         {   // the key kernel is bound by the latency of random table reads: every wave the CU can hold
             int per_cu = tuning().key_blocks_per_cu;
-            const uint32_t ac = ascii_cap_of(db, 0);
-            const size_t smem_k = (size_t)WAVES_PER_BLOCK * (ac + (db.direct ? 4u * (((ac >> 4) + 2 + 3) & ~3u) : 0u) + 16u);
-            // (the instance the default knobs launch: forward windows only, at most 64 of them -- two slots, not the placement kernel's five)
-            const bool two_slots = !tuning().order_both_strands && tuning().order_windows <= 64;
-            const void* kfn = fast_mode(db) == 2 ? (two_slots ? (const void*)order_key_kernel<2, true, true, true> : (const void*)order_key_kernel<CLS_SLOTS[0], true, true, true>)
-                              : db.addr32 ? (two_slots ? (const void*)order_key_kernel<2, true, true, false> : (const void*)order_key_kernel<CLS_SLOTS[0], true, true, false>)
-                                          : (two_slots ? (const void*)order_key_kernel<2, false, true, false> : (const void*)order_key_kernel<CLS_SLOTS[0], false, true, false>);
-            if (per_cu <= 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 64 * WAVES_PER_BLOCK, smem_k) != hipSuccess || per_cu <= 0)) per_cu = 4;
+            const KeyKernel k = key_kernel(db, true);
+            if (per_cu <= 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn(), 64 * WAVES_PER_BLOCK, k.smem) != hipSuccess || per_cu <= 0)) per_cu = 4;
             // (MurmurHash3 front: waves finish their reads at very different times; twice the resident grid evens the tail
             // out: C3s35 keys 2.7 -> 2.1 ms)
             if (tuning().key_blocks_per_cu <= 0 && fast_mode(db) == 2) per_cu *= 2;
@@ -2520,14 +2553,11 @@ PlacePlan plan_place(const DbDev& db, uint32_t n_reads, uint32_t n_cu, bool stat
     if (tile_usable(db)) {
         p.tile_from = tuning().tile_min_kmers > 0 ? std::min<uint32_t>(blk_cap, (uint32_t)tuning().tile_min_kmers) : (uint32_t)(64 * CLS_SLOTS[1]);
         if (p.max_kmers > p.tile_from) {
-            p.tile = tile_plan(db, p.tile_from, p.max_kmers, n_reads, n_cu);
+            p.tile = tile_plan(db, stats, p.tile_from, p.max_kmers, n_reads, n_cu);
             p.tiled = p.tile.whole.cap_kmers > p.tile_from;
         }
     }
     if (p.tiled) {
-        p.time_tile = p.max_kmers > MAX_READ_KMERS || tuning().time_class == 2;
-        p.tile_name_threads = p.tile.whole.threads;
-        for (uint32_t i = p.tile.n_sub; i-- > 0;) if (p.tile.sub[i].cap_kmers >= p.max_kmers) p.tile_name_threads = p.tile.sub[i].threads;
         p.tile_off_words = w;
         w += p.tile.scratch_words;
         w += w & 1;
@@ -2549,6 +2579,12 @@ PlacePlan plan_place(const DbDev& db, uint32_t n_reads, uint32_t n_cu, bool stat
         w += p.long_stride_words * p.grid_long;
     }
     p.ws_bytes = w * 4;
+    p.blk = p.max_kmers > (uint32_t)(64 * CLS_SLOTS[1]) && (!p.tiled || p.tile_from > (uint32_t)(64 * CLS_SLOTS[1]));
+    // the timed launch: the LDS-tiled one in a launch provisioned for long reads; CLS_TIME_CLASS=2 (a bench of gene-length
+    // reads): the LDS-tiled or the workgroup-per-read one, whichever the launch has; else class 0
+    const bool gene = tuning().time_class == 2;
+    p.timed = p.tiled && (p.max_kmers > MAX_READ_KMERS || gene) ? PlacePlan::TIME_TILE : p.blk && gene ? PlacePlan::TIME_BLOCK : PlacePlan::TIME_CLASS0;
+    p.timed_name = p.timed == PlacePlan::TIME_TILE ? p.tile.name : p.timed == PlacePlan::TIME_BLOCK ? block_kernel(db, stats).name : class_kernel(db, 0, stats).name;
     return p;
 }
 
@@ -2567,7 +2603,6 @@ hipError_t launch_place(const DbDev& db, const PlaceParams& prm, const PlacePlan
     const uint32_t profile_stop = (uint32_t)tuning().profile_stop;
     const uint32_t ws_stride = child_ws_stride(db);
     const bool st = d_stats != nullptr;
-    const bool binary = db.max_nonleaf_arity <= 2;
     auto classify = [&](const uint32_t* order) {
         ClassCaps caps{};
         caps.cap[0] = (uint32_t)(64 * CLS_SLOTS[0]);
@@ -2578,151 +2613,90 @@ hipError_t launch_place(const DbDev& db, const PlaceParams& prm, const PlacePlan
             caps.cap[6] = plan.tile.whole.cap_kmers;
         }
         caps.cap[7] = plan.long_cap;
-        hipLaunchKernelGGL(classify_kernel, dim3((n_reads + CLASSIFY_THREADS * CLASSIFY_PER_THREAD - 1) / (CLASSIFY_THREADS * CLASSIFY_PER_THREAD)), dim3(CLASSIFY_THREADS), 0, stream,
-                           d_offsets, order, n_reads, db.k, caps, lists[0], counts, d_out, d_stats);
+        return launch_kernel(classify_kernel, dim3((n_reads + CLASSIFY_THREADS * CLASSIFY_PER_THREAD - 1) / (CLASSIFY_THREADS * CLASSIFY_PER_THREAD)), dim3(CLASSIFY_THREADS), 0,
+                             stream, d_offsets, order, n_reads, db.k, caps, lists[0], counts, d_out, d_stats);
     };
     const uint32_t* list0 = lists[0];
     uint32_t list0_n = 0, xcd_chunks = 0;
-    if (!plan.ordered) classify(nullptr);
-    if (plan.ordered) {
+    if (!plan.ordered) e = classify(nullptr);
+    else {
         uint64_t* keys_in = reinterpret_cast<uint64_t*>(d_ws + plan.keys_off_words);
         uint64_t* keys_out = keys_in + n_reads;
         uint32_t* idx_in = reinterpret_cast<uint32_t*>(keys_out + n_reads);
         uint32_t* idx_out = idx_in + n_reads;
-        const uint32_t ac = ascii_cap_of(db, 0);
         const Tuning& tn = tuning();
         const uint32_t key_mode = (uint32_t)tn.order_mode;
-        const uint32_t fwd_only = tn.order_both_strands ? 0u : 1u;
-        const uint32_t sample_shift = (uint32_t)tn.order_sample_shift;
         const uint32_t block_shift = (uint32_t)tn.order_block_shift;
-        const size_t smem_k = (size_t)WAVES_PER_BLOCK * (ac + (db.direct ? 4u * (((ac >> 4) + 2 + 3) & ~3u) : 0u) + 16u);
-        // windows of a read that make its key (CLS_ORDER_WINDOWS; 64 = one lookup slot per lane, 160 = all of a 150 bp read)
-        const uint32_t key_windows = (uint32_t)tn.order_windows;
         // the reads that get a key: those of the two wave-per-read classes and, when the launch has them, of the LDS-tiled classes
         // (by their first windows: reads of one neighbourhood of the tree then share table lines, set records and split halves in L2)
         const uint32_t key_cap = (plan.tiled && !tn.no_tile_order) ? 0xFFFFFFFFu : (uint32_t)(64 * CLS_SLOTS[1]);
-#define CLS_LAUNCH_KEY_S(SL, A32, FW, HS)                                                                                                 \
-    hipLaunchKernelGGL((order_key_kernel<SL, A32, FW, HS>), dim3(plan.grid_key), dim3(64 * WAVES_PER_BLOCK), smem_k, stream, db,          \
-                       d_bases, d_offsets, n_reads, keys_in, idx_in, ac, key_mode, block_shift, sample_shift, fwd_only,                    \
-                       key_cap)
-#define CLS_LAUNCH_KEY(A32, HS)                                                                                                           \
-    do {                                                                                                                                  \
-        if (fwd_only && key_windows <= 64) CLS_LAUNCH_KEY_S(2, A32, true, HS);                                                            \
-        else if (fwd_only) CLS_LAUNCH_KEY_S(CLS_SLOTS[0], A32, true, HS);                                                                 \
-        else CLS_LAUNCH_KEY_S(CLS_SLOTS[0], A32, false, HS);                                                                              \
-    } while (0)
-        if (fast_mode(db) != 2 && fwd_only && key_windows == 64 && sample_shift >= 32) {
-            // (the default: two reads per wavefront)
+        const KeyKernel k = key_kernel(db, false);
+        const dim3 block(64 * WAVES_PER_BLOCK);
+        if (k.half) {  // (two reads per wavefront)
             const uint32_t grid_half = std::max<uint32_t>(1, std::min<uint32_t>((n_reads + 2 * WAVES_PER_BLOCK - 1) / (2 * WAVES_PER_BLOCK), plan.grid_key));
-            if (db.addr32)
-                hipLaunchKernelGGL((order_key_half_kernel<true>), dim3(grid_half), dim3(64 * WAVES_PER_BLOCK), 0, stream, db, d_bases, d_offsets,
-                                   n_reads, keys_in, idx_in, key_mode, block_shift, key_cap);
-            else
-                hipLaunchKernelGGL((order_key_half_kernel<false>), dim3(grid_half), dim3(64 * WAVES_PER_BLOCK), 0, stream, db, d_bases, d_offsets,
-                                   n_reads, keys_in, idx_in, key_mode, block_shift, key_cap);
+            e = launch_kernel(k.half, dim3(grid_half), block, k.smem, stream, db, d_bases, d_offsets, n_reads, keys_in, idx_in, key_mode, block_shift, key_cap);
+        } else {
+            e = launch_kernel(k.full, dim3(plan.grid_key), block, k.smem, stream, db, d_bases, d_offsets, n_reads, keys_in, idx_in, ascii_cap_of(db, 0), key_mode,
+                              block_shift, (uint32_t)tn.order_sample_shift, tn.order_both_strands ? 0u : 1u, key_cap);
         }
-        else if (fast_mode(db) == 2) CLS_LAUNCH_KEY(true, true);
-        else if (db.addr32) CLS_LAUNCH_KEY(true, false);
-        else CLS_LAUNCH_KEY(false, false);
-#undef CLS_LAUNCH_KEY
-#undef CLS_LAUNCH_KEY_S
+        if (e != hipSuccess) return e;
         e = order_reads(d_ws + plan.sort_off_words, keys_in, idx_out, n_reads, order_key_bits(db) - 1, stream);  // (- 1: the bit that only the all-ones "no key" sets)
         if (e != hipSuccess) return e;
         list0 = idx_out;
         list0_n = n_reads;
         xcd_chunks = 1;
-        classify(idx_out);  // (after the order: the lists of the LDS-tiled classes come out in locality order)
+        e = classify(idx_out);  // (after the order: the lists of the LDS-tiled classes come out in locality order)
     }
-    auto launch_class = [&](auto slots_c, auto bits_c, int c) {
-        constexpr int SLOTS = decltype(slots_c)::value, SET_BITS = decltype(bits_c)::value;
+    if (e != hipSuccess) return e;
+    auto launch_class = [&](int c) {
+        const ClassKernel k = class_kernel(db, c, st);
         const dim3 grid(plan.grid[c]), block(64 * WAVES_PER_BLOCK);
-        const uint32_t seq_cap = seq_cap_of(db, c);
-        const size_t smem = smem_of(db, c);
-        if (use_fast(db)) {
-            const uint32_t ac = ascii_cap_of(db, c);
-            const uint32_t* lst = xcd_chunks ? list0 : lists[c];  // ordered: one list for both classes, each skips the other's reads
-            const uint32_t ln = list0_n, xc = xcd_chunks;
-#define CLS_LAUNCH_FAST(ST, A32, MD, PO)                                                                                              \
-    hipLaunchKernelGGL((place_fast_kernel<SLOTS, SET_BITS, ST, A32, MD, PO>), grid, block, smem, stream, db, prm, d_bases, d_offsets, \
-                       lst, counts + c, ln, xc, d_out, d_stats, ac, profile_stop)
-#define CLS_LAUNCH_FAST3(ST, A32, MD) do { if (db.binary_tree) CLS_LAUNCH_FAST(ST, A32, MD, false); else CLS_LAUNCH_FAST(ST, A32, MD, true); } while (0)
-#define CLS_LAUNCH_FAST2(ST, A32) do { if (db.canonical) CLS_LAUNCH_FAST3(ST, A32, 1); else CLS_LAUNCH_FAST3(ST, A32, 0); } while (0)
-            if (fast_mode(db) == 2) { if (st) CLS_LAUNCH_FAST3(true, true, 2); else CLS_LAUNCH_FAST3(false, true, 2); }
-            else if (fast_mode(db) == 3 && db.addr32) { if (st) CLS_LAUNCH_FAST3(true, true, 3); else CLS_LAUNCH_FAST3(false, true, 3); }
-            else if (fast_mode(db) == 4 && db.addr32) { if (st) CLS_LAUNCH_FAST3(true, true, 4); else CLS_LAUNCH_FAST3(false, true, 4); }
-            else if (db.addr32) { if (st) CLS_LAUNCH_FAST2(true, true); else CLS_LAUNCH_FAST2(false, true); }
-            else { if (st) CLS_LAUNCH_FAST2(true, false); else CLS_LAUNCH_FAST2(false, false); }
-#undef CLS_LAUNCH_FAST2
-#undef CLS_LAUNCH_FAST3
-#undef CLS_LAUNCH_FAST
-            return;
+        if (k.fast) {  // (ordered: one list for both classes, each skips the other's reads)
+            return launch_kernel(k.fast, grid, block, k.smem, stream, db, prm, d_bases, d_offsets, xcd_chunks ? list0 : lists[c], counts + c, list0_n, xcd_chunks,
+                                 d_out, d_stats, ascii_cap_of(db, c), profile_stop);
         }
-        if (db.format == FMT_SPLIT) {
-#define CLS_LAUNCH_SPLIT(ST, PO)                                                                                        \
-    hipLaunchKernelGGL((place_split_kernel<SLOTS, SET_BITS, ST, PO>), grid, block, smem, stream, db, prm, d_bases, d_offsets, \
-                       lists[c], counts + c, d_out, d_stats, seq_cap, profile_stop, child_ws, ws_stride)
-            if (db.binary_tree) { if (st) CLS_LAUNCH_SPLIT(true, false); else CLS_LAUNCH_SPLIT(false, false); }
-            else { if (st) CLS_LAUNCH_SPLIT(true, true); else CLS_LAUNCH_SPLIT(false, true); }
-#undef CLS_LAUNCH_SPLIT
-            return;
-        }
-#define CLS_LAUNCH(ST, BI)                                                                                          \
-    hipLaunchKernelGGL((place_wave_kernel<SLOTS, SET_BITS, ST, BI>), grid, block, smem, stream, db, prm, d_bases,  \
-                       d_offsets, lists[c], counts + c, d_out, d_stats, seq_cap, child_ws, ws_stride)
-        if (st) { if (binary) CLS_LAUNCH(true, true); else CLS_LAUNCH(true, false); }
-        else { if (binary) CLS_LAUNCH(false, true); else CLS_LAUNCH(false, false); }
-#undef CLS_LAUNCH
+        if (k.split)
+            return launch_kernel(k.split, grid, block, k.smem, stream, db, prm, d_bases, d_offsets, lists[c], counts + c, d_out, d_stats, seq_cap_of(db, c),
+                                 profile_stop, child_ws, ws_stride);
+        return launch_kernel(k.wave, grid, block, k.smem, stream, db, prm, d_bases, d_offsets, lists[c], counts + c, d_out, d_stats, seq_cap_of(db, c), child_ws,
+                             ws_stride);
     };
-    // the timed kernel (cls_db_kernel_time): the LDS-tiled long-read kernel in a launch provisioned for long reads,
-    // else the wave-per-read kernel of the <= 320-k-mer class
-    const bool time_tile = plan.time_tile, time_blk = !time_tile && tuning().time_class == 2;  // (time_class 2: a bench of gene-length reads times the workgroup-per-read kernel)
-    if (ev_start && !time_tile && !time_blk) (void)hipEventRecord(ev_start, stream);
-    if (set_bits_of(db, 0) != CLS_SET_BITS[0]) launch_class(std::integral_constant<int, CLS_SLOTS[0]>{}, std::integral_constant<int, NARROW_CANON_BITS>{}, 0);
-    else launch_class(std::integral_constant<int, CLS_SLOTS[0]>{}, std::integral_constant<int, CLS_SET_BITS[0]>{}, 0);
-    if (ev_stop && !time_tile && !time_blk) (void)hipEventRecord(ev_stop, stream);
-    if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
-    if (plan.max_kmers > (uint32_t)(64 * CLS_SLOTS[0])) launch_class(std::integral_constant<int, CLS_SLOTS[1]>{}, std::integral_constant<int, CLS_SET_BITS[1]>{}, 1);
-    if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
-    if (plan.max_kmers > (uint32_t)(64 * CLS_SLOTS[1]) && (!plan.tiled || plan.tile_from > (uint32_t)(64 * CLS_SLOTS[1]))) {   // class 2: one workgroup per read (the generic probe path, whatever the index format)
-        const dim3 grid(plan.grid_blk), block(64 * BLK_WAVES);
-        const uint32_t seq_cap = blk_seq_cap(db);
-        const size_t smem = blk_smem(db);
-        if (ev_start && time_blk) (void)hipEventRecord(ev_start, stream);
-#define CLS_LAUNCH_BLK(ST, BI, SP)                                                                                              \
-    do {                                                                                                                        \
-        auto kfn = place_block_kernel<BLK_WAVES, BLK_SLOTS, BLK_SET_BITS, ST, BI, SP>;                                          \
-        (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); /* > 64 KiB of LDS */ \
-        hipLaunchKernelGGL(kfn, grid, block, smem, stream, db, prm, d_bases, d_offsets, lists[2], counts + 2, d_out, d_stats,    \
-                           seq_cap, child_ws, ws_stride);                                                                        \
-    } while (0)
-        if (db.format == FMT_SPLIT && db.binary_tree) { if (st) CLS_LAUNCH_BLK(true, true, true); else CLS_LAUNCH_BLK(false, true, true); }
-        else if (db.format == FMT_SPLIT) { if (st) CLS_LAUNCH_BLK(true, false, true); else CLS_LAUNCH_BLK(false, false, true); }
-        else if (binary) { if (st) CLS_LAUNCH_BLK(true, true, false); else CLS_LAUNCH_BLK(false, true, false); }
-        else { if (st) CLS_LAUNCH_BLK(true, false, false); else CLS_LAUNCH_BLK(false, false, false); }
-#undef CLS_LAUNCH_BLK
-        if (ev_stop && time_blk) (void)hipEventRecord(ev_stop, stream);
+    // the HIP events go around the launch plan.timed
+    auto timed = [&](PlacePlan::Timed t, auto&& launch) {
+        if (ev_start && plan.timed == t) (void)hipEventRecord(ev_start, stream);
+        const hipError_t r = launch();
+        if (ev_stop && plan.timed == t) (void)hipEventRecord(ev_stop, stream);
+        return r;
+    };
+    e = timed(PlacePlan::TIME_CLASS0, [&] { return launch_class(0); });
+    if (e != hipSuccess) return e;
+    if (plan.max_kmers > (uint32_t)(64 * CLS_SLOTS[0])) {
+        e = launch_class(1);
+        if (e != hipSuccess) return e;
+    }
+    if (plan.blk) {  // class 2: one workgroup per read (the generic probe path, whatever the index format)
+        const auto k = block_kernel(db, st);
+        e = timed(PlacePlan::TIME_BLOCK, [&] {
+            return launch_kernel(k.fn, dim3(plan.grid_blk), dim3(64 * BLK_WAVES), k.smem, stream, db, prm, d_bases, d_offsets, lists[2], counts + 2, d_out, d_stats,
+                                 blk_seq_cap(db), child_ws, ws_stride);
+        });
+        if (e != hipSuccess) return e;
     }
     if (plan.tiled) {  // classes 3 .. 6: every state in LDS; reads the kernel cannot hold are appended to class 7's list
-        if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
-        if (ev_start && time_tile) (void)hipEventRecord(ev_start, stream);
         const uint32_t* sub_lists[TILE_MAX_SUB] = {lists[3], lists[4], lists[5]};
         const uint32_t* sub_lens[TILE_MAX_SUB] = {counts + 3, counts + 4, counts + 5};
-        tile_launch(db, prm, plan.tile, st, d_bases, d_offsets, sub_lists, sub_lens, lists[6], counts + 6, d_out, d_stats, lists[7], counts + 7,
-                    d_ws + plan.tile_off_words, plan.ordered && !tuning().no_tile_order, stream);
-        if (ev_stop && time_tile) (void)hipEventRecord(ev_stop, stream);
+        e = timed(PlacePlan::TIME_TILE, [&] {
+            return tile_launch(db, prm, plan.tile, st, d_bases, d_offsets, sub_lists, sub_lens, lists[6], counts + 6, d_out, d_stats, lists[7], counts + 7,
+                               d_ws + plan.tile_off_words, plan.ordered && !tuning().no_tile_order, stream);
+        });
+        if (e != hipSuccess) return e;
     }
     if (plan.grid_long) {  // class 7: reads beyond what the LDS holds (and every long read of the other index shapes): state in the workspace
-        if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
-        uint32_t* lws = d_ws + plan.long_off_words;
-#define CLS_LAUNCH_LONG(SP, ST)                                                                                                 \
-    hipLaunchKernelGGL((place_long_kernel<SP, ST>), dim3(plan.grid_long), dim3(LONG_THREADS), 0, stream, db, prm, d_bases, d_offsets, \
-                       lists[7], counts + 7, d_out, d_stats, lws, plan.long_stride_words, plan.long_cap, (uint32_t)plan.long_set,  \
-                       plan.long_arity)
-        if (db.format == FMT_SPLIT) { if (st) CLS_LAUNCH_LONG(true, true); else CLS_LAUNCH_LONG(true, false); }
-        else { if (st) CLS_LAUNCH_LONG(false, true); else CLS_LAUNCH_LONG(false, false); }
-#undef CLS_LAUNCH_LONG
+        const auto k = long_kernel(db, st);
+        e = launch_kernel(k.fn, dim3(plan.grid_long), dim3(LONG_THREADS), k.smem, stream, db, prm, d_bases, d_offsets, lists[7], counts + 7, d_out, d_stats,
+                          d_ws + plan.long_off_words, plan.long_stride_words, plan.long_cap, (uint32_t)plan.long_set, plan.long_arity);
     }
-    return hipGetLastError();
+    return e;
 }
 
 }  // namespace cls

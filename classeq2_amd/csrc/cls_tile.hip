@@ -644,18 +644,18 @@ __global__ __launch_bounds__(THREADS, 4) void place_tile_kernel(DbDev db, PlaceP
     }
 }
 
-const void* tile_kernel(uint32_t threads, int front, bool stats, bool a32, bool poly) {
-#define CLS_RT4(TH, FR, ST, A) (poly ? (const void*)place_tile_kernel<TH, FR, ST, A, true> : (const void*)place_tile_kernel<TH, FR, ST, A, false>)
-#define CLS_RT3(TH, FR, ST) (a32 ? CLS_RT4(TH, FR, ST, true) : CLS_RT4(TH, FR, ST, false))
-#define CLS_RT2(TH, FR) (stats ? CLS_RT3(TH, FR, true) : CLS_RT3(TH, FR, false))
-#define CLS_RT1(TH) (front == 2 ? CLS_RT2(TH, 2) : front == 1 ? CLS_RT2(TH, 1) : CLS_RT2(TH, 0))
-    return threads == 128 ? CLS_RT1(128) : threads == 256 ? CLS_RT1(256) : threads == 512 ? CLS_RT1(512) : CLS_RT1(1024);
-#undef CLS_RT1
-#undef CLS_RT2
-#undef CLS_RT3
-#undef CLS_RT4
-}
 int tile_front(const DbDev& db) { return db.direct == nullptr ? 2 : db.canonical ? 1 : 0; }
+// the instance of the one kernel that runs configuration `c`
+auto tile_kernel(const DbDev& db, bool stats, const TileCfg& c) {
+    auto of = [&](auto threads) {
+        auto inst = [&](auto... v) { return pick(place_tile_kernel<decltype(v)::value...>, c.smem, "place_tile_kernel", v...); };
+        return with_bool(stats, [&](auto st) { return with_bool(db.addr32 != 0, [&](auto a32) { return with_bool(!db.binary_tree, [&](auto poly) {
+            const int front = tile_front(db);
+            return front == 2 ? inst(threads, Int<2>{}, st, a32, poly) : front == 1 ? inst(threads, Int<1>{}, st, a32, poly) : inst(threads, Int<0>{}, st, a32, poly);
+        }); }); });
+    };
+    return c.threads == 128 ? of(Int<128>{}) : c.threads == 256 ? of(Int<256>{}) : c.threads == 512 ? of(Int<512>{}) : of(Int<1024>{});
+}
 
 }  // namespace
 
@@ -672,7 +672,7 @@ bool tile_usable(const DbDev& db) {
 // on 1.9 kb reads: 1.8x over 2), each for the reads whose front fits its share of the LDS -- what is left of the share after
 // the read (and the word per lookup) is the code set -- while the descent still holds an entry for every second lookup; a
 // read with more entries than that is handed to the WHOLE launch.
-TilePlan tile_plan(const DbDev& db, uint32_t from_kmers, uint32_t max_kmers, uint32_t n_reads, uint32_t n_cu) {
+TilePlan tile_plan(const DbDev& db, bool stats, uint32_t from_kmers, uint32_t max_kmers, uint32_t n_reads, uint32_t n_cu) {
     TilePlan p{};
     const bool hashed = tile_front(db) == 2, canon = !hashed && db.canonical != 0;
     const uint32_t per_look = canon ? 2u : 1u;  // k-mers a lookup stands for (canonical: one per window)
@@ -727,36 +727,33 @@ TilePlan tile_plan(const DbDev& db, uint32_t from_kmers, uint32_t max_kmers, uin
         c.scratch_off = p.scratch_words;
         p.scratch_words += (uint64_t)rt_scratch_words(c.cap_entries) * c.grid;
     }
+    const TileCfg* longest = &p.whole;
+    for (uint32_t i = p.n_sub; i-- > 0;) if (p.sub[i].cap_kmers >= max_kmers) longest = &p.sub[i];
+    p.name = tile_kernel(db, stats, *longest).name;
     return p;
 }
 
-std::string tile_kernel_name(const DbDev& db, bool stats, uint32_t threads) {
-    auto b = [](bool v) { return std::string(v ? "true" : "false"); };
-    return "place_tile_kernel<" + std::to_string(threads) + ", " + std::to_string(tile_front(db)) + ", " + b(stats) + ", " + b(db.addr32 != 0) + ", " + b(!db.binary_tree) + ">";
-}
-
-void tile_launch(const DbDev& db, const PlaceParams& prm, const TilePlan& p, bool stats, const uint8_t* d_bases, const uint64_t* d_offsets,
-                 const uint32_t* const* sub_lists, const uint32_t* const* sub_lens, uint32_t* big_list, uint32_t* big_len,
-                 cls_placement* d_out, cls_query_stats* d_stats, uint32_t* spill_list, uint32_t* spill_len, uint32_t* scratch, bool ordered, hipStream_t stream) {
+hipError_t tile_launch(const DbDev& db, const PlaceParams& prm, const TilePlan& p, bool stats, const uint8_t* d_bases, const uint64_t* d_offsets,
+                       const uint32_t* const* sub_lists, const uint32_t* const* sub_lens, uint32_t* big_list, uint32_t* big_len,
+                       cls_placement* d_out, cls_query_stats* d_stats, uint32_t* spill_list, uint32_t* spill_len, uint32_t* scratch, bool ordered, hipStream_t stream) {
     // `over`: where a read with more entries than the launch holds goes -- from a shared launch to the WHOLE one, from that
     // (hashed front only) to the workspace kernel
     auto launch = [&](const TileCfg& c, const uint32_t* lst, const uint32_t* len, uint32_t* over_list, uint32_t* over_len) {
-        const void* kfn = tile_kernel(c.threads, tile_front(db), stats, db.addr32 != 0, !db.binary_tree);
-        (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.smem);
-        uint32_t max_lookups = c.lookups, max_bases = c.bases, set_words = c.set_words, cap_entries = c.cap_entries;
-        uint32_t* gws = scratch + c.scratch_off;
-        uint32_t xcd_walk = ordered ? (uint32_t)std::max(1, tuning().tile_deal) : 0u;
+        const uint32_t xcd_walk = ordered ? (uint32_t)std::max(1, tuning().tile_deal) : 0u;
         // the code set: every code in one pass at load <= 0.5 (knobs: fewer words / codes per pass -- tests)
+        uint32_t set_words = c.set_words;
         if (tuning().tile_set_words > 0) set_words = std::min<uint32_t>(set_words, (uint32_t)tuning().tile_set_words);
         uint32_t pass_codes = std::max<uint32_t>(1u, set_words / 2);
         if (tuning().tile_pass_codes > 0) pass_codes = (uint32_t)tuning().tile_pass_codes;
-        void* args[] = {(void*)&db, (void*)&prm, (void*)&d_bases, (void*)&d_offsets, (void*)&lst, (void*)&len, (void*)&d_out, (void*)&d_stats,
-                        (void*)&max_lookups, (void*)&max_bases, (void*)&pass_codes, (void*)&set_words, (void*)&spill_list, (void*)&spill_len,
-                        (void*)&cap_entries, (void*)&gws, (void*)&over_list, (void*)&over_len, (void*)&xcd_walk};
-        (void)hipLaunchKernel(kfn, dim3(c.grid), dim3(c.threads), args, c.smem, stream);
+        const auto k = tile_kernel(db, stats, c);
+        return launch_kernel(k.fn, dim3(c.grid), dim3(c.threads), k.smem, stream, db, prm, d_bases, d_offsets, lst, len, d_out, d_stats, c.lookups,
+                             c.bases, pass_codes, set_words, spill_list, spill_len, c.cap_entries, scratch + c.scratch_off, over_list, over_len, xcd_walk);
     };
-    for (uint32_t i = 0; i < p.n_sub; ++i) launch(p.sub[i], sub_lists[i], sub_lens[i], big_list, big_len);
-    launch(p.whole, big_list, big_len, spill_list, spill_len);
+    for (uint32_t i = 0; i < p.n_sub; ++i) {
+        const hipError_t e = launch(p.sub[i], sub_lists[i], sub_lens[i], big_list, big_len);
+        if (e != hipSuccess) return e;
+    }
+    return launch(p.whole, big_list, big_len, spill_list, spill_len);
 }
 
 }  // namespace cls

@@ -20,6 +20,7 @@ struct Tuning {
     int no_tile_order = 0;        // CLS_NO_TILE_ORDER: the LDS-tiled classes' reads in batch order, not in locality order
     int tile_one_per_cu = 0;      // CLS_TILE_ONE_PER_CU: the LDS-tiled kernel as ONE 1024-thread workgroup a CU even where two 512-thread ones fit
     int time_class = 0;           // CLS_TIME_CLASS: 2 = cls_db_kernel_time / cls_db_kernel_name follow the workgroup-per-read kernel (reads of 513..4096 + k - 1 bases)
+                                  // or the LDS-tiled one, whichever the launch has (neither: the class-0 kernel)
     int blocks_per_cu = 0;        // CLS_BLOCKS_PER_CU: grid of the wave-per-read kernels (0: what is resident)
     int key_blocks_per_cu = 0;    // CLS_KEY_BLOCKS_PER_CU
     int long_blocks_per_cu = 2;   // CLS_LONG_BLOCKS_PER_CU: workspace long-read kernel

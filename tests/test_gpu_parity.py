@@ -139,6 +139,26 @@ def test_declared_read_length_drops_the_classes_beyond_it():
         assert len(records_equal(db.place_batch(bases, offsets), want)) == 0
 
 
+def test_time_class_2_without_the_workgroup_kernel_names_and_times_class_0():
+    """CLS_TIME_CLASS=2 asks for the workgroup-per-read kernel; a launch provisioned for 150 bp reads (300 k-mers) has
+    none, so the class-0 kernel is the one named and timed: one event pair per chunk."""
+    s = SynthDb(300, 600, 10, 4)
+    bases, offsets, _ = s.reads(2000, 150)
+    n = 3
+    engine.set_tuning("time_class", 2)
+    try:
+        with engine.PlacementDb(s.flat, device=0) as db:
+            db.set_max_read_len(150)
+            assert db.kernel_name().startswith("place_fast_kernel<"), db.kernel_name()
+            db.kernel_time(reset=True)
+            for _ in range(n):
+                db.place_batch(bases, offsets)  # (2000 reads: one chunk)
+            ms, launches = db.kernel_time(reset=True)
+            assert launches == n and ms > 0, (ms, launches)
+    finally:
+        engine.set_tuning("time_class", 0)
+
+
 @pytest.mark.parametrize("k,collapse,drop,deep", [(15, 0.0, 0.0, 0), (12, 0.4, 0.0, 0), (11, 0.3, 0.2, 0), (15, 0.0, 0.0, 1), (20, 0.5, 0.0, 1)])
 def test_long_reads_workspace_kernel(k, collapse, drop, deep):
     """Reads of 4.2..11 kb (BASELINE config 5 has 10 kb reads): more k-mers than the register-resident kernels
