@@ -129,6 +129,15 @@ class DbInfo(C.Structure):
     ]
 
 
+class ReadClass(C.Structure):
+    """cls_read_class (cls_db_read_classes)."""
+    _fields_ = [
+        ("list", C.c_uint32),
+        ("max_kmers", C.c_uint32),
+        ("kernel", C.c_char * 112),
+    ]
+
+
 class Fasta(C.Structure):
     _fields_ = [
         ("n", C.c_uint32),

@@ -101,6 +101,7 @@ struct cls_db {
     std::mutex ws_mu;
     uint64_t max_read_len = 0;  // what the device-buffer entry provisions its long-read slices for (0: none, reads of up to
                                 // MAX_READ_KMERS k-mers only; cls_db_set_max_read_len opts in)
+                                // (info.max_read_kmers is not kept: cls_db_info_get takes it from the plan, device_plan)
     double kernel_ms_sum = 0.0;
     uint64_t kernel_launches = 0;
     std::vector<Workspace> ws;  // per-call scratch (class lists, child counters), recycled once their launch has finished
@@ -263,7 +264,6 @@ extern "C" int cls_db_create(const cls_db_desc* d, int device, cls_db** out) {
         i.table_slots = E.table.size();
         i.postings_words = E.postings.size();
         i.hbm_bytes = E.nodes.size() * sizeof(cls::DNode) + E.table.size() * sizeof(cls::Slot) + (E.postings.size() + E.postings2.size()) * 4 + E.bucket_key.size() * 8 + E.mz_bucket.size() * 4 + E.direct.size() * 4 + E.direct16.size() * 4 + (E.sets.size() + E.sets2.size()) * sizeof(cls::SetRec);
-        i.max_read_kmers = db->max_read_len ? (uint32_t)std::max<uint64_t>(320, 2 * db->max_read_len) : cls::MAX_READ_KMERS;
         i.device = device;
         i.format = E.format;
         i.binary_tree = E.strictly_binary ? 1u : 0u;
@@ -295,13 +295,33 @@ extern "C" int cls_db_validate(const cls_db_desc* d) {
     }
 }
 
+// The plan cls_place_batch_device() makes for reads of up to n_bases bases (0: its default, reads of up to MAX_READ_KMERS
+// k-mers); the host-buffer entries plan each chunk the same way from its longest read.  The class limits and the kernel
+// instances do not depend on the batch size.
+static cls::PlacePlan device_plan(const cls_db* db, uint64_t n_bases, bool stats) {
+    return cls::plan_place(db->dev, 4096, (uint32_t)db->n_cu, stats, (uint32_t)(2 * n_bases), n_bases ? 4096 : 0);
+}
+
+static uint64_t declared_read_len(const cls_db* db) {
+    std::lock_guard<std::mutex> g(const_cast<cls_db*>(db)->ws_mu);
+    return db->max_read_len;
+}
+
 extern "C" int cls_db_info_get(const cls_db* db, cls_db_info* info) {
     if (!db || !info) return fail(CLS_E_INVALID_ARG, "cls_db_info_get: null argument");
-    cls_db* mdb = const_cast<cls_db*>(db);
-    std::lock_guard<std::mutex> g(mdb->ws_mu);
-    *info = db->info;
-    info->scratch_slots = (uint32_t)db->ws.size();
-    return CLS_OK;
+    try {
+        // the largest read the device-buffer entry's plan places, as it would launch now (declared read length, knobs)
+        uint32_t cap[cls::N_LISTS];
+        device_plan(db, declared_read_len(db), false).class_caps(cap);
+        cls_db* mdb = const_cast<cls_db*>(db);
+        std::lock_guard<std::mutex> g(mdb->ws_mu);
+        *info = db->info;
+        info->scratch_slots = (uint32_t)db->ws.size();
+        info->max_read_kmers = *std::max_element(cap, cap + cls::N_LISTS);
+        return CLS_OK;
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_db_info_get: unknown exception");
+    }
 }
 
 extern "C" int cls_db_info_get2(const cls_db* db, void* info, size_t info_size) {
@@ -413,7 +433,6 @@ extern "C" int cls_db_set_max_read_len(cls_db* db, uint64_t n_bases) {
     if (n_bases > HARD_MAX_READ_LEN) return fail(CLS_E_INVALID_ARG, "cls_db_set_max_read_len: at most 2^25 bases per read");
     std::lock_guard<std::mutex> g(db->ws_mu);
     db->max_read_len = n_bases;
-    db->info.max_read_kmers = (uint32_t)std::max<uint64_t>(cls::MAX_READ_KMERS, 2 * n_bases);
     return CLS_OK;
 }
 
@@ -484,14 +503,37 @@ extern "C" int cls_place_batch_device(cls_db* db, const void* d_bases, const voi
 extern "C" int cls_db_kernel_name(const cls_db* db, char* buf, size_t len) {
     if (!db || !buf || !len) return fail(CLS_E_INVALID_ARG, "cls_db_kernel_name: null argument");
     try {
-        uint64_t max_len;
-        { std::lock_guard<std::mutex> g(const_cast<cls_db*>(db)->ws_mu); max_len = db->max_read_len; }
-        // (as cls_place_batch_device would plan a launch: long reads only when the caller opted in)
-        const cls::PlacePlan plan = cls::plan_place(db->dev, 4096, (uint32_t)db->n_cu, false, (uint32_t)(2 * max_len), max_len ? 4096 : 0);
-        snprintf(buf, len, "%s", plan.timed_name.c_str());
+        snprintf(buf, len, "%s", device_plan(db, declared_read_len(db), false).timed_name.c_str());
         return CLS_OK;
     } catch (...) {
         return fail(CLS_E_INTERNAL, "cls_db_kernel_name: unknown exception");
+    }
+}
+
+extern "C" int cls_db_read_classes(const cls_db* db, uint64_t n_bases, int stats, cls_read_class* out, int max, int* n_out) {
+    if (!db || !n_out || max < 0 || (max > 0 && !out)) return fail(CLS_E_INVALID_ARG, "cls_db_read_classes: null argument");
+    if (n_bases > HARD_MAX_READ_LEN) return fail(CLS_E_INVALID_ARG, "cls_db_read_classes: at most 2^25 bases per read");
+    try {
+        const cls::PlacePlan plan = device_plan(db, n_bases, stats != 0);
+        uint32_t cap[cls::N_LISTS];
+        plan.class_caps(cap);
+        // a list takes the reads above every earlier list's limit and up to its own (classify_kernel): those with none are left out
+        int n = 0;
+        uint32_t below = 0;
+        for (int c = 0; c < cls::N_LISTS; ++c) {
+            if (c > 0 && cap[c] <= below) continue;
+            below = cap[c];
+            if (n < max) {
+                out[n].list = (uint32_t)c;
+                out[n].max_kmers = cap[c];
+                snprintf(out[n].kernel, sizeof out[n].kernel, "%s", plan.class_kernel_name(db->dev, c, stats != 0).c_str());
+            }
+            ++n;
+        }
+        *n_out = n;
+        return CLS_OK;
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_db_read_classes: unknown exception");
     }
 }
 

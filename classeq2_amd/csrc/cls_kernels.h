@@ -65,6 +65,10 @@ struct TilePlan {
     std::string name;  // instance of the configuration that takes the longest read planned for
 };
 
+// Read-length class lists (classify_kernel): 0, 1 the wave-per-read kernels; 2 the workgroup-per-read kernel; 3 .. 5 the
+// shared launches of the LDS-tiled kernel; 6 its whole-CU launch; 7 the workspace kernel
+constexpr int N_LISTS = 8;
+
 // Grid sizes + scratch layout of one placement batch.
 struct PlacePlan {
     uint32_t grid[2];          // workgroups per wave-per-read class
@@ -92,10 +96,16 @@ struct PlacePlan {
     enum Timed : uint8_t { TIME_CLASS0, TIME_BLOCK, TIME_TILE } timed;
     std::string timed_name;
     uint64_t ws_bytes;         // device scratch the launch needs
+    // The one source of the class limits: list c takes the reads of up to cap[c] k-mers that no list before it takes
+    // (0: not in this launch).  classify_kernel bins by them; cls_db_info.max_read_kmers and cls_db_read_classes report them.
+    void class_caps(uint32_t (&cap)[N_LISTS]) const;
+    // instance name of the kernel that places list c's reads
+    std::string class_kernel_name(const DbDev& db, int c, bool stats) const;
 };
 // LDS-tiled long-read kernel (cls_tile.hip): launch interface
 bool tile_usable(const DbDev& db);
 TilePlan tile_plan(const DbDev& db, bool stats, uint32_t from_kmers, uint32_t max_kmers, uint32_t n_reads, uint32_t n_cu);
+std::string tile_kernel_name(const DbDev& db, bool stats, const TileCfg& c);
 // reads of the shared launches' lists and of `big_list` (device) -> records; reads the kernel cannot hold (its code set, its
 // entries) are appended to `spill_list`
 hipError_t tile_launch(const DbDev& db, const PlaceParams& prm, const TilePlan& p, bool stats, const uint8_t* d_bases, const uint64_t* d_offsets,

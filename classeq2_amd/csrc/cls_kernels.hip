@@ -2295,8 +2295,7 @@ __global__ __launch_bounds__(LONG_THREADS) void place_long_kernel(DbDev db, Plac
 constexpr int CLASSIFY_THREADS = 256, CLASSIFY_PER_THREAD = 4;
 // class lists: 0, 1 the wave-per-read kernels; 2 the workgroup-per-read kernel; 3 .. 5 the shared launches of the LDS-tiled
 // kernel; 6 its launch that gives a read a whole CU (and the list the shared launches hand reads on to); 7 the workspace
-// kernel (and the list the LDS-tiled kernel spills to)
-constexpr int N_LISTS = 8;
+// kernel (and the list the LDS-tiled kernel spills to); their limits: PlacePlan::class_caps
 struct ClassCaps { uint32_t cap[N_LISTS]; };  // class c takes the reads of up to cap[c] k-mers that no class before it takes (0: not in this launch)
 __global__ __launch_bounds__(CLASSIFY_THREADS) void classify_kernel(const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ order, uint32_t n_reads, uint32_t k, ClassCaps caps,
                                                                    uint32_t* __restrict__ lists, uint32_t* __restrict__ counts,
@@ -2491,6 +2490,26 @@ KeyKernel key_kernel(const DbDev& db, bool sizing) {
 }
 }  // namespace
 
+void PlacePlan::class_caps(uint32_t (&cap)[N_LISTS]) const {
+    for (uint32_t& c : cap) c = 0;
+    cap[0] = (uint32_t)(64 * CLS_SLOTS[0]);
+    if (max_kmers > cap[0]) cap[1] = (uint32_t)(64 * CLS_SLOTS[1]);
+    if (max_kmers > (uint32_t)(64 * CLS_SLOTS[1])) cap[2] = tiled ? tile_from : (uint32_t)(64 * BLK_WAVES * BLK_SLOTS);
+    if (tiled) {
+        for (uint32_t i = 0; i < tile.n_sub; ++i) cap[3 + i] = tile.sub[i].cap_kmers;
+        cap[6] = tile.whole.cap_kmers;
+    }
+    cap[7] = long_cap;
+}
+
+std::string PlacePlan::class_kernel_name(const DbDev& db, int c, bool stats) const {
+    if (c < 2) return class_kernel(db, c, stats).name;
+    if (c == 2) return block_kernel(db, stats).name;
+    if (c < 6) return tile_kernel_name(db, stats, tile.sub[c - 3]);
+    if (c == 6) return tile_kernel_name(db, stats, tile.whole);
+    return long_kernel(db, stats).name;
+}
+
 PlacePlan plan_place(const DbDev& db, uint32_t n_reads, uint32_t n_cu, bool stats, uint32_t long_cap, uint32_t n_long) {
     PlacePlan p{};
     // persistent-style grids: exactly the blocks that are resident at once (every wave then strides
@@ -2605,14 +2624,7 @@ hipError_t launch_place(const DbDev& db, const PlaceParams& prm, const PlacePlan
     const bool st = d_stats != nullptr;
     auto classify = [&](const uint32_t* order) {
         ClassCaps caps{};
-        caps.cap[0] = (uint32_t)(64 * CLS_SLOTS[0]);
-        if (plan.max_kmers > caps.cap[0]) caps.cap[1] = (uint32_t)(64 * CLS_SLOTS[1]);
-        if (plan.max_kmers > (uint32_t)(64 * CLS_SLOTS[1])) caps.cap[2] = plan.tiled ? plan.tile_from : (uint32_t)(64 * BLK_WAVES * BLK_SLOTS);
-        if (plan.tiled) {
-            for (uint32_t i = 0; i < plan.tile.n_sub; ++i) caps.cap[3 + i] = plan.tile.sub[i].cap_kmers;
-            caps.cap[6] = plan.tile.whole.cap_kmers;
-        }
-        caps.cap[7] = plan.long_cap;
+        plan.class_caps(caps.cap);
         return launch_kernel(classify_kernel, dim3((n_reads + CLASSIFY_THREADS * CLASSIFY_PER_THREAD - 1) / (CLASSIFY_THREADS * CLASSIFY_PER_THREAD)), dim3(CLASSIFY_THREADS), 0,
                              stream, d_offsets, order, n_reads, db.k, caps, lists[0], counts, d_out, d_stats);
     };

@@ -733,6 +733,8 @@ TilePlan tile_plan(const DbDev& db, bool stats, uint32_t from_kmers, uint32_t ma
     return p;
 }
 
+std::string tile_kernel_name(const DbDev& db, bool stats, const TileCfg& c) { return tile_kernel(db, stats, c).name; }
+
 hipError_t tile_launch(const DbDev& db, const PlaceParams& prm, const TilePlan& p, bool stats, const uint8_t* d_bases, const uint64_t* d_offsets,
                        const uint32_t* const* sub_lists, const uint32_t* const* sub_lens, uint32_t* big_list, uint32_t* big_len,
                        cls_placement* d_out, cls_query_stats* d_stats, uint32_t* spill_list, uint32_t* spill_len, uint32_t* scratch, bool ordered, hipStream_t stream) {

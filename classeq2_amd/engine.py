@@ -23,7 +23,7 @@ _LIB = None
 
 EXPORTS = [
     "cls_device_count", "cls_db_create", "cls_db_validate", "cls_db_destroy", "cls_db_info_get", "cls_db_info_get2", "cls_db_kernel_time", "cls_db_kernel_name",
-    "cls_db_set_max_read_len", "cls_place_batch",
+    "cls_db_read_classes", "cls_db_set_max_read_len", "cls_place_batch",
     "cls_place_batch_device", "cls_place_batch_stats", "cls_fasta_parse", "cls_fasta_free", "cls_fasta_scan_device", "cls_fasta_dev_free",
     "cls_fasta_parse_gpu", "cls_place_fasta_text", "cls_last_error",
     "cls_version", "cls_set_tuning", "cls_tuning_from_env",
@@ -70,6 +70,8 @@ def lib():
         L.cls_db_kernel_time.restype = i32
         L.cls_db_kernel_name.argtypes = [vp, C.c_char_p, C.c_size_t]
         L.cls_db_kernel_name.restype = i32
+        L.cls_db_read_classes.argtypes = [vp, C.c_uint64, i32, C.POINTER(_abi.ReadClass), i32, C.POINTER(i32)]
+        L.cls_db_read_classes.restype = i32
         L.cls_db_set_max_read_len.argtypes = [vp, C.c_uint64]
         L.cls_db_set_max_read_len.restype = i32
         L.cls_place_batch.argtypes = [vp, vp, vp, u32, C.POINTER(_abi.Params), vp]
@@ -239,6 +241,16 @@ class PlacementDb:
         buf = C.create_string_buffer(256)
         _check(lib().cls_db_kernel_name(self._h, buf, len(buf)))
         return buf.value.decode()
+
+    def read_classes(self, n_bases: int = 0, stats: bool = False):
+        """Test and measurement aid (cls_db_read_classes): the read-length classes of a device-buffer launch provisioned
+        for reads of up to `n_bases` bases (0: the default), in binning order -> [(list, max_kmers, kernel instance)].
+        Follows the tuning knobs at the time of the call."""
+        buf = (_abi.ReadClass * 8)()
+        n = C.c_int(0)
+        _check(lib().cls_db_read_classes(self._h, n_bases, 1 if stats else 0, buf, len(buf), C.byref(n)))
+        assert n.value <= len(buf)
+        return [(int(c.list), int(c.max_kmers), c.kernel.decode()) for c in buf[:n.value]]
 
     def place_batch(self, bases: np.ndarray, offsets: np.ndarray, params: Optional[_abi.Params] = None,
                     want_stats: bool = False, out: Optional[np.ndarray] = None):

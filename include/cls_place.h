@@ -183,7 +183,8 @@ typedef struct cls_db_info {
     uint64_t table_slots;
     uint64_t postings_words;
     uint64_t hbm_bytes;        /* device bytes held by the handle                */
-    uint32_t max_read_kmers;   /* per-read k-mer capacity of the device-buffer entry */
+    uint32_t max_read_kmers;   /* per-read k-mer capacity of the device-buffer entry as it would launch now (declared
+                                * read length, tuning knobs): the largest read it places; longer ones are CLS_ERR_READ_TOO_LONG */
     int32_t device;
     uint32_t format;           /* 0: sorted lists (some node set is not closed under `parent`); 1: split-tree records */
     uint32_t binary_tree;      /* 1: every clade has zero or two children        */
@@ -233,8 +234,9 @@ int cls_place_batch_device(cls_db* db, const void* d_bases, const void* d_offset
  * longer reads are reported CLS_ERR_READ_TOO_LONG.  With n_bases set, the launch follows it: the read-length classes
  * beyond n_bases are not launched (a batch of 150 bp reads then costs one placement kernel, not one per class) and a
  * read longer than n_bases may be reported CLS_ERR_READ_TOO_LONG; a caller with reads beyond 8192 k-mers opts in
- * here.  Reads the LDS-tiled kernel cannot hold keep their per-k-mer state in the workspace: 80 bytes per base and
- * resident workgroup.  At most 2^25. */
+ * here.  cls_db_info.max_read_kmers reports the capacity that results (n_bases = 160: 320 k-mers).  Reads the
+ * LDS-tiled kernel cannot hold keep their per-k-mer state in the workspace: 80 bytes per base and resident workgroup.
+ * At most 2^25. */
 int cls_db_set_max_read_len(cls_db* db, uint64_t n_bases);
 
 /* Device time of the DOMINANT placement kernel (the wave-per-read kernel of the
@@ -248,6 +250,19 @@ int cls_db_kernel_time(cls_db* db, double* sum_ms, uint64_t* launches, int reset
 /* Name (template instance, as rocprofv3 prints it without the argument list) of that dominant kernel for this
  * handle, without statistics: lets bench.py tie a committed profile to the kernel it really launches. */
 int cls_db_kernel_name(const cls_db* db, char* buf, size_t len);
+
+/* Test and measurement aid, not part of the Rust shim's surface: the read-length classes of a cls_place_batch_device()
+ * launch provisioned for reads of up to n_bases bases (as after cls_db_set_max_read_len(db, n_bases); 0: its default) --
+ * a host-buffer call plans each chunk the same way from its longest read -- in the order the reads are binned: class `list`
+ * takes the reads of up to `max_kmers` k-mers (2(L - k + 1)) that no class before it takes, placed by the kernel instance
+ * `kernel` (as cls_db_kernel_name names it).  `stats` != 0: the instances of a launch with per-query counters.  Follows
+ * the tuning knobs at the time of the call.  Writes at most `max` entries; *n_out = how many classes there are. */
+typedef struct cls_read_class {
+    uint32_t list;         /* class list, 0 .. 7                                  */
+    uint32_t max_kmers;    /* the longest read (k-mers) the class takes           */
+    char kernel[112];
+} cls_read_class;          /* 120 bytes */
+int cls_db_read_classes(const cls_db* db, uint64_t n_bases, int stats, cls_read_class* out, int max, int* n_out);
 
 /* Host-buffer variant that also returns the per-query counters. */
 int cls_place_batch_stats(cls_db* db, const char* bases, const uint64_t* offsets, uint32_t n,

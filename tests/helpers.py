@@ -38,16 +38,17 @@ def stats_equal(a: np.ndarray, b: np.ndarray):
     return np.nonzero(bad)[0]
 
 
-def device_place(db, bases, offsets, params=None, want_stats=True):
-    """cls_place_batch_device on torch-owned HBM buffers (cuda:0) -> (records, stats)."""
+def device_place(db, bases, offsets, params=None, want_stats=True, fill=0):
+    """cls_place_batch_device on torch-owned HBM buffers (cuda:0) -> (records, stats).  `fill`: the byte the output
+    buffers hold before the launch (0xFF: a record no kernel writes cannot pass for a real one)."""
     import torch
 
     dev = torch.device("cuda:0")
     n = len(offsets) - 1
     d_b = torch.from_numpy(bases if len(bases) else np.zeros(1, np.uint8)).to(dev)
     d_o = torch.from_numpy(offsets.astype(np.int64)).to(dev)
-    d_out = torch.zeros(n * 24, dtype=torch.uint8, device=dev)
-    d_st = torch.zeros(n * 24, dtype=torch.uint8, device=dev)
+    d_out = torch.full((n * 24,), fill, dtype=torch.uint8, device=dev)
+    d_st = torch.full((n * 24,), fill, dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()
     db.place_batch_device(d_b.data_ptr(), d_o.data_ptr(), n, d_out.data_ptr(), params, d_st.data_ptr() if want_stats else 0, 0)
     torch.cuda.synchronize()
@@ -55,7 +56,9 @@ def device_place(db, bases, offsets, params=None, want_stats=True):
 
 
 def describe(rec) -> str:
-    return f"{_abi.STATUS_NAMES[int(rec['status'])]} one={rec['one']} rest={rec['rest']} levels={rec['levels']} clade={rec['clade_id']}"
+    st = int(rec["status"])
+    name = _abi.STATUS_NAMES[st] if st < len(_abi.STATUS_NAMES) else f"status {st} (never written)"
+    return f"{name} one={rec['one']} rest={rec['rest']} levels={rec['levels']} clade={rec['clade_id']}"
 
 
 def drop_random_nodes(flat: FlatDb, frac: float, seed: int, keep_root_frac: float = 0.9) -> FlatDb:

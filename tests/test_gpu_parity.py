@@ -5,7 +5,7 @@ import pytest
 from classeq2_amd import _abi, engine
 from classeq2_amd.synth import CONFIGS, SynthDb
 from oracle import oracle_port as op
-from tests.helpers import (ODD_PARAM_SETS, PARAM_SETS, describe, drop_random_nodes, ragged_reads, records_equal, stats_equal,
+from tests.helpers import (ODD_PARAM_SETS, PARAM_SETS, describe, device_place, drop_random_nodes, ragged_reads, records_equal, stats_equal,
                            truncate_random_sets)
 
 pytestmark = pytest.mark.gpu
@@ -85,34 +85,18 @@ def test_ragged_and_edge_reads():
     assert (got2["status"][victims] == _abi.ERR_INVALID_BASE).all()
 
 
-def _device_place(db, bases, offsets, want_stats=True):
-    """cls_place_batch_device on torch-owned HBM buffers."""
-    import torch
-
-    dev = torch.device("cuda:0")
-    n = len(offsets) - 1
-    d_b = torch.from_numpy(bases if len(bases) else np.zeros(1, np.uint8)).to(dev)
-    d_o = torch.from_numpy(offsets.astype(np.int64)).to(dev)
-    d_out = torch.zeros(n * 24, dtype=torch.uint8, device=dev)
-    d_st = torch.zeros(n * 24, dtype=torch.uint8, device=dev)
-    torch.cuda.synchronize()
-    db.place_batch_device(d_b.data_ptr(), d_o.data_ptr(), n, d_out.data_ptr(), None, d_st.data_ptr() if want_stats else 0, 0)
-    torch.cuda.synchronize()
-    return d_out.cpu().numpy().view(_abi.PLACEMENT_DTYPE), d_st.cpu().numpy().view(_abi.STATS_DTYPE)
-
-
 def test_read_too_long_reported():
     """The device-buffer entry provisions for the handle's max_read_len; beyond it reads are refused, not misplaced."""
     s = SynthDb(30, 21000, 9, 4)
     bases, offsets, _ = s.reads(6, 20000)
     with engine.PlacementDb(s.flat, device=0) as db:
         assert 2 * (20000 - 9 + 1) > db.info.max_read_kmers
-        got, st = _device_place(db, bases, offsets)
+        got, st = device_place(db, bases, offsets)
         assert (got["status"] == _abi.ERR_READ_TOO_LONG).all()
         assert (st["n_query_kmers"] == 2 * (20000 - 9 + 1)).all()
         db.set_max_read_len(20000)
         assert db.info.max_read_kmers == 40000
-        got2, st2 = _device_place(db, bases, offsets)
+        got2, st2 = device_place(db, bases, offsets)
         host, hst = db.place_batch(bases, offsets, want_stats=True)  # sizes itself by the batch
     want, wst = op.OraclePort(s.flat).place_batch(bases, offsets, op.make_params(), threads=8, want_stats=True)
     assert len(records_equal(got2, want)) == 0 and len(records_equal(host, want)) == 0
@@ -129,9 +113,11 @@ def test_declared_read_length_drops_the_classes_beyond_it():
     offsets = np.concatenate([parts[0][1], parts[1][1][1:] + parts[0][1][-1]])
     want = op.OraclePort(s.flat).place_batch(bases, offsets, op.make_params(), threads=8)
     with engine.PlacementDb(s.flat, device=0) as db:
-        for n_bases, refused in ((0, False), (160, True), (290, True), (1000, False)):
+        # (max_read_kmers: the largest read the launch then places -- 2n once the LDS-tiled kernel takes the longest)
+        for n_bases, refused, capacity in ((0, False, 8192), (160, True, 320), (290, True, 1024), (1000, False, 2000)):
             db.set_max_read_len(n_bases)
-            got, _ = _device_place(db, bases, offsets)
+            assert db.info.max_read_kmers == capacity, (n_bases, db.info.max_read_kmers)
+            got, _ = device_place(db, bases, offsets)
             assert len(records_equal(got[:-1], want[:-1])) == 0
             assert (got["status"][-1] == _abi.ERR_READ_TOO_LONG) == refused
             if not refused:
@@ -339,7 +325,7 @@ def test_host_entry_pipelines_large_batches():
     bases, offsets, _ = s.reads(n, 100)
     with engine.PlacementDb(s.flat, device=0) as db:
         host, hst = db.place_batch(bases, offsets, want_stats=True)
-        dev, dst = _device_place(db, bases, offsets)
+        dev, dst = device_place(db, bases, offsets)
         host2 = db.place_batch(bases, offsets)
     assert len(records_equal(host, dev)) == 0 and len(stats_equal(hst, dst)) == 0 and len(records_equal(host2, dev)) == 0
     pick = np.random.default_rng(1).choice(n, 20000, replace=False)

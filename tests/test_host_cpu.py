@@ -31,6 +31,7 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_abi.Node) == 32 and C.sizeof(_abi.Placement) == 24 and C.sizeof(_abi.QueryStats) == 24
     assert _abi.Placement.clade_id.offset == 16 and _abi.Placement.levels.offset == 12
     assert C.sizeof(_abi.DbDesc) == 96 and _abi.DbDesc.node_set_kind.offset == 88
+    assert C.sizeof(_abi.ReadClass) == 120 and _abi.ReadClass.kernel.offset == 8
 
 
 def test_validate_accepts_generated_dbs():
