@@ -187,91 +187,105 @@ extern "C" void cls_db_destroy(cls_db* db) {
     delete db;
 }
 
+// Validation + re-encoding of a descriptor, for cls_db_create and cls_db_group_create (`who`: the entry's name).
+static int encode(const cls_db_desc* d, cls::EncodedDb& E, const char* who) {
+    std::string err;
+    int rc = cls::encode_db(d, E, err);
+    if (rc != CLS_OK) return fail(rc, std::string(who) + ": " + err);
+    if (E.format == cls::FMT_LIST && E.postings.size() >= (1ULL << 32)) return fail(CLS_E_BAD_DB, std::string(who) + ": sorted-list postings exceed 2^32 words");
+    return CLS_OK;
+}
+
+// The device half of cls_db_create: an encoded index -> a handle on `device` (-1: the current device).  `n_buckets`:
+// the descriptor's, for cls_db_info.  Leaves `device` current on the calling thread.  May throw std::bad_alloc.
+static int upload(const cls::EncodedDb& E, uint32_t n_buckets, int device, cls_db** out) {
+    *out = nullptr;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+        return fail(CLS_E_NO_DEVICE, "cls_db_create: no HIP device is visible (the placement path has no CPU fallback)");
+    if (device < 0) CLS_HIP(hipGetDevice(&device));
+    if (device >= n_dev) return fail(CLS_E_INVALID_ARG, "cls_db_create: device ordinal out of range");
+    CLS_HIP(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    CLS_HIP(hipGetDeviceProperties(&prop, device));
+    cls_db* db = new cls_db();
+    db->device = device;
+    db->n_cu = prop.multiProcessorCount;
+    auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(dst, bytes + 64);  // (tail pad: the kernels read node records in pairs and 16-byte entries speculatively)
+        if (e != hipSuccess) return e;
+        return bytes ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    };
+    hipError_t e;
+    if ((e = up(&db->d_nodes, E.nodes.data(), E.nodes.size() * sizeof(cls::DNode))) != hipSuccess ||
+        (e = up(&db->d_kids, E.kids.data(), E.kids.size() * 4)) != hipSuccess ||
+        (e = up(&db->d_table, E.table.data(), E.table.size() * sizeof(cls::Slot))) != hipSuccess ||
+        (e = up(&db->d_postings, E.postings.data(), E.postings.size() * 4)) != hipSuccess ||
+        (!E.postings2.empty() && (e = up(&db->d_postings2, E.postings2.data(), E.postings2.size() * 4)) != hipSuccess) ||
+        (e = up(&db->d_bucket_key, E.bucket_key.data(), E.bucket_key.size() * 8)) != hipSuccess ||
+        (!E.mz_bucket.empty() && (e = up(&db->d_mz_bucket, E.mz_bucket.data(), E.mz_bucket.size() * 4)) != hipSuccess) ||
+        (!E.direct.empty() && (e = up(&db->d_direct, E.direct.data(), E.direct.size() * 4)) != hipSuccess) ||
+        (!E.direct16.empty() && (e = up(&db->d_direct16, E.direct16.data(), E.direct16.size() * 4)) != hipSuccess) ||
+        (!E.sets.empty() && (e = up(&db->d_sets, E.sets.data(), E.sets.size() * sizeof(cls::SetRec))) != hipSuccess) ||
+        (!E.sets2.empty() && (e = up(&db->d_sets2, E.sets2.data(), E.sets2.size() * sizeof(cls::SetRec))) != hipSuccess)) {
+        cls_db_destroy(db);
+        return fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string("cls_db_create: upload failed: ") + hipGetErrorString(e));
+    }
+    cls::DbDev& v = db->dev;
+    v.nodes = (const cls::DNode*)db->d_nodes;
+    v.kids = (const uint32_t*)db->d_kids;
+    v.table = (const cls::Slot*)db->d_table;
+    v.postings = (const uint32_t*)db->d_postings;
+    v.postings2 = (const uint32_t*)db->d_postings2;
+    v.bucket_key = (const uint64_t*)db->d_bucket_key;
+    v.mz_bucket = (const uint32_t*)db->d_mz_bucket;
+    v.direct = (const uint32_t*)db->d_direct;
+    v.direct16 = (const uint32_t*)db->d_direct16;
+    v.sets = (const cls::SetRec*)db->d_sets;
+    v.sets2 = (const cls::SetRec*)db->d_sets2;
+    v.table_mask = E.table.size() - 1;
+    v.n_nodes = (uint32_t)E.nodes.size();
+    v.n_buckets = (uint32_t)E.bucket_key.size();
+    v.k = E.k;
+    v.m_eff = E.m_eff;
+    v.max_nonleaf_arity = E.max_nonleaf_arity;
+    v.format = E.format;
+    v.binary_tree = E.strictly_binary ? 1u : 0u;
+    v.canonical = E.canonical ? 1u : 0u;
+    v.n_sets = (uint32_t)E.sets.size();
+    v.set_bits = 1;
+    while (v.set_bits < 32 && (1ull << v.set_bits) < (uint64_t)E.sets.size()) ++v.set_bits;
+    v.addr32 = (E.postings.size() * 4 < (1ull << 32) && E.direct.size() * 4 < (1ull << 32) && E.sets.size() * sizeof(cls::SetRec) < (1ull << 32)) ? 1u : 0u;
+    cls_db_info& i = db->info;
+    i.n_nodes = v.n_nodes;
+    i.max_depth = E.max_depth;
+    i.max_nonleaf_arity = E.max_nonleaf_arity;
+    i.k_size = E.k;
+    i.m_size = E.m;
+    i.n_buckets = n_buckets;
+    i.n_kmers = E.n_kmers;
+    i.n_closed_kmers = E.n_closed;
+    i.table_slots = E.table.size();
+    i.postings_words = E.postings.size();
+    i.hbm_bytes = E.nodes.size() * sizeof(cls::DNode) + E.table.size() * sizeof(cls::Slot) + (E.postings.size() + E.postings2.size()) * 4 + E.bucket_key.size() * 8 + E.mz_bucket.size() * 4 + E.direct.size() * 4 + E.direct16.size() * 4 + (E.sets.size() + E.sets2.size()) * sizeof(cls::SetRec);
+    i.device = device;
+    i.format = E.format;
+    i.binary_tree = E.strictly_binary ? 1u : 0u;
+    i.direct_table = E.direct.empty() ? 0u : (E.canonical ? 2u : 1u);
+    i.n_tip_sets = (uint32_t)E.n_sets;
+    i.fat_direct_table = E.direct16.empty() ? 0u : 1u;
+    *out = db;
+    return CLS_OK;
+}
+
 extern "C" int cls_db_create(const cls_db_desc* d, int device, cls_db** out) {
     if (!out) return fail(CLS_E_INVALID_ARG, "cls_db_create: out is null");
     *out = nullptr;
     try {
         cls::EncodedDb E;
-        std::string err;
-        int rc = cls::encode_db(d, E, err);
-        if (rc != CLS_OK) return fail(rc, "cls_db_create: " + err);
-        if (E.format == cls::FMT_LIST && E.postings.size() >= (1ULL << 32)) return fail(CLS_E_BAD_DB, "cls_db_create: sorted-list postings exceed 2^32 words");
-        int n_dev = 0;
-        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
-            return fail(CLS_E_NO_DEVICE, "cls_db_create: no HIP device is visible (the placement path has no CPU fallback)");
-        if (device < 0) CLS_HIP(hipGetDevice(&device));
-        if (device >= n_dev) return fail(CLS_E_INVALID_ARG, "cls_db_create: device ordinal out of range");
-        CLS_HIP(hipSetDevice(device));
-        hipDeviceProp_t prop;
-        CLS_HIP(hipGetDeviceProperties(&prop, device));
-        cls_db* db = new cls_db();
-        db->device = device;
-        db->n_cu = prop.multiProcessorCount;
-        auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-            hipError_t e = hipMalloc(dst, bytes + 64);  // (tail pad: the kernels read node records in pairs and 16-byte entries speculatively)
-            if (e != hipSuccess) return e;
-            return bytes ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
-        };
-        hipError_t e;
-        if ((e = up(&db->d_nodes, E.nodes.data(), E.nodes.size() * sizeof(cls::DNode))) != hipSuccess ||
-            (e = up(&db->d_kids, E.kids.data(), E.kids.size() * 4)) != hipSuccess ||
-            (e = up(&db->d_table, E.table.data(), E.table.size() * sizeof(cls::Slot))) != hipSuccess ||
-            (e = up(&db->d_postings, E.postings.data(), E.postings.size() * 4)) != hipSuccess ||
-            (!E.postings2.empty() && (e = up(&db->d_postings2, E.postings2.data(), E.postings2.size() * 4)) != hipSuccess) ||
-            (e = up(&db->d_bucket_key, E.bucket_key.data(), E.bucket_key.size() * 8)) != hipSuccess ||
-            (!E.mz_bucket.empty() && (e = up(&db->d_mz_bucket, E.mz_bucket.data(), E.mz_bucket.size() * 4)) != hipSuccess) ||
-            (!E.direct.empty() && (e = up(&db->d_direct, E.direct.data(), E.direct.size() * 4)) != hipSuccess) ||
-            (!E.direct16.empty() && (e = up(&db->d_direct16, E.direct16.data(), E.direct16.size() * 4)) != hipSuccess) ||
-            (!E.sets.empty() && (e = up(&db->d_sets, E.sets.data(), E.sets.size() * sizeof(cls::SetRec))) != hipSuccess) ||
-            (!E.sets2.empty() && (e = up(&db->d_sets2, E.sets2.data(), E.sets2.size() * sizeof(cls::SetRec))) != hipSuccess)) {
-            cls_db_destroy(db);
-            return fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string("cls_db_create: upload failed: ") + hipGetErrorString(e));
-        }
-        cls::DbDev& v = db->dev;
-        v.nodes = (const cls::DNode*)db->d_nodes;
-        v.kids = (const uint32_t*)db->d_kids;
-        v.table = (const cls::Slot*)db->d_table;
-        v.postings = (const uint32_t*)db->d_postings;
-        v.postings2 = (const uint32_t*)db->d_postings2;
-        v.bucket_key = (const uint64_t*)db->d_bucket_key;
-        v.mz_bucket = (const uint32_t*)db->d_mz_bucket;
-        v.direct = (const uint32_t*)db->d_direct;
-        v.direct16 = (const uint32_t*)db->d_direct16;
-        v.sets = (const cls::SetRec*)db->d_sets;
-        v.sets2 = (const cls::SetRec*)db->d_sets2;
-        v.table_mask = E.table.size() - 1;
-        v.n_nodes = (uint32_t)E.nodes.size();
-        v.n_buckets = (uint32_t)E.bucket_key.size();
-        v.k = E.k;
-        v.m_eff = E.m_eff;
-        v.max_nonleaf_arity = E.max_nonleaf_arity;
-        v.format = E.format;
-        v.binary_tree = E.strictly_binary ? 1u : 0u;
-        v.canonical = E.canonical ? 1u : 0u;
-        v.n_sets = (uint32_t)E.sets.size();
-        v.set_bits = 1;
-        while (v.set_bits < 32 && (1ull << v.set_bits) < (uint64_t)E.sets.size()) ++v.set_bits;
-        v.addr32 = (E.postings.size() * 4 < (1ull << 32) && E.direct.size() * 4 < (1ull << 32) && E.sets.size() * sizeof(cls::SetRec) < (1ull << 32)) ? 1u : 0u;
-        cls_db_info& i = db->info;
-        i.n_nodes = v.n_nodes;
-        i.max_depth = E.max_depth;
-        i.max_nonleaf_arity = E.max_nonleaf_arity;
-        i.k_size = E.k;
-        i.m_size = E.m;
-        i.n_buckets = (uint32_t)d->n_buckets;
-        i.n_kmers = E.n_kmers;
-        i.n_closed_kmers = E.n_closed;
-        i.table_slots = E.table.size();
-        i.postings_words = E.postings.size();
-        i.hbm_bytes = E.nodes.size() * sizeof(cls::DNode) + E.table.size() * sizeof(cls::Slot) + (E.postings.size() + E.postings2.size()) * 4 + E.bucket_key.size() * 8 + E.mz_bucket.size() * 4 + E.direct.size() * 4 + E.direct16.size() * 4 + (E.sets.size() + E.sets2.size()) * sizeof(cls::SetRec);
-        i.device = device;
-        i.format = E.format;
-        i.binary_tree = E.strictly_binary ? 1u : 0u;
-        i.direct_table = E.direct.empty() ? 0u : (E.canonical ? 2u : 1u);
-        i.n_tip_sets = (uint32_t)E.n_sets;
-        i.fat_direct_table = E.direct16.empty() ? 0u : 1u;
-        *out = db;
-        return CLS_OK;
+        int rc = encode(d, E, "cls_db_create");
+        if (rc != CLS_OK) return rc;
+        return upload(E, (uint32_t)d->n_buckets, device, out);
     } catch (const std::bad_alloc&) {
         return fail(CLS_E_NOMEM, "cls_db_create: out of host memory");
     } catch (const std::exception& ex) {
@@ -547,13 +561,29 @@ extern "C" int cls_db_kernel_time(cls_db* db, double* sum_ms, uint64_t* launches
     return CLS_OK;
 }
 
+// The buffer checks of the host-buffer entries (n > 0).
+static int check_host_args(const char* bases, const uint64_t* offsets, uint32_t n, const cls_placement* out) {
+    if (!offsets || !out || (!bases && offsets[n] != offsets[0])) return fail(CLS_E_INVALID_ARG, "cls_place_batch: null buffer");
+    for (uint32_t i = 0; i < n; ++i)
+        if (offsets[i] > offsets[i + 1]) return fail(CLS_E_INVALID_ARG, "cls_place_batch: offsets not monotone");
+    return CLS_OK;
+}
+
+static int place_host_checked(cls_db* db, const char* bases, const uint64_t* offsets, uint32_t n, const cls_params* params,
+                              cls_placement* out, cls_query_stats* stats);
+
 static int place_host(cls_db* db, const char* bases, const uint64_t* offsets, uint32_t n, const cls_params* params,
                       cls_placement* out, cls_query_stats* stats) {
     if (!db) return fail(CLS_E_INVALID_ARG, "cls_place_batch: null handle");
     if (n == 0) return CLS_OK;
-    if (!offsets || !out || (!bases && offsets[n] != offsets[0])) return fail(CLS_E_INVALID_ARG, "cls_place_batch: null buffer");
-    for (uint32_t i = 0; i < n; ++i)
-        if (offsets[i] > offsets[i + 1]) return fail(CLS_E_INVALID_ARG, "cls_place_batch: offsets not monotone");
+    const int rc = check_host_args(bases, offsets, n, out);
+    if (rc != CLS_OK) return rc;
+    return place_host_checked(db, bases, offsets, n, params, out, stats);
+}
+
+// place_host once its arguments are checked (n > 0); saves and restores the calling thread's current device.
+static int place_host_checked(cls_db* db, const char* bases, const uint64_t* offsets, uint32_t n, const cls_params* params,
+                              cls_placement* out, cls_query_stats* stats) {
     int prev = 0;
     CLS_HIP(hipGetDevice(&prev));
     CLS_HIP(hipSetDevice(db->device));
@@ -674,6 +704,163 @@ extern "C" int cls_place_batch_stats(cls_db* db, const char* bases, const uint64
                                      const cls_params* params, cls_placement* out, cls_query_stats* stats) {
     if (!stats) return fail(CLS_E_INVALID_ARG, "cls_place_batch_stats: stats is null");
     return place_host(db, bases, offsets, n, params, out, stats);
+}
+
+// ---- index groups: one index encoded once, uploaded to several devices --------------------------------------------
+
+struct cls_db_group {
+    std::vector<cls_db*> replicas;  // replica i lives on devices[i]
+    std::vector<int> devices;
+};
+
+extern "C" void cls_db_group_destroy(cls_db_group* g) {
+    if (!g) return;
+    for (cls_db* db : g->replicas) cls_db_destroy(db);
+    delete g;
+}
+
+extern "C" int cls_db_group_create(const cls_db_desc* d, const int* devices, uint32_t n_devices, cls_db_group** out) {
+    if (!out) return fail(CLS_E_INVALID_ARG, "cls_db_group_create: out is null");
+    *out = nullptr;
+    cls_db_group* g = nullptr;
+    try {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+            return fail(CLS_E_NO_DEVICE, "cls_db_group_create: no HIP device is visible (the placement path has no CPU fallback)");
+        std::vector<int> devs;
+        if (!devices || n_devices == 0) {
+            for (int i = 0; i < n_dev; ++i) devs.push_back(i);
+        } else {
+            for (uint32_t i = 0; i < n_devices; ++i) {
+                if (devices[i] < 0 || devices[i] >= n_dev)
+                    return fail(CLS_E_INVALID_ARG, "cls_db_group_create: device ordinal " + std::to_string(devices[i]) + " out of range (" +
+                                                       std::to_string(n_dev) + " visible)");
+                devs.push_back(devices[i]);
+            }
+        }
+        cls::EncodedDb E;
+        int rc = encode(d, E, "cls_db_group_create");
+        if (rc != CLS_OK) return rc;
+        const size_t n = devs.size();
+        g = new cls_db_group();
+        g->devices = devs;
+        g->replicas.assign(n, nullptr);
+        // one host thread per replica: the copies to the devices overlap, and the caller's current device is untouched
+        std::vector<int> rcs(n, CLS_E_INTERNAL);
+        std::vector<std::string> msgs(n, "upload thread not started");
+        auto work = [&](size_t i) {
+            try {
+                rcs[i] = upload(E, (uint32_t)d->n_buckets, devs[i], &g->replicas[i]);
+                if (rcs[i] != CLS_OK) msgs[i] = g_err;
+            } catch (const std::bad_alloc&) {
+                rcs[i] = CLS_E_NOMEM;
+                msgs[i] = "out of host memory";
+            } catch (...) {
+                rcs[i] = CLS_E_INTERNAL;
+                msgs[i] = "unknown exception";
+            }
+        };
+        std::vector<std::thread> th;
+        try {
+            for (size_t i = 0; i < n; ++i) th.emplace_back(work, i);
+        } catch (...) {  // (a thread that could not be started leaves its replica's error in place)
+        }
+        for (auto& t : th) t.join();
+        for (size_t i = 0; i < n; ++i) {
+            if (rcs[i] == CLS_OK) continue;
+            const std::string m = "cls_db_group_create: replica " + std::to_string(i) + " (device " + std::to_string(devs[i]) + "): " + msgs[i];
+            rc = rcs[i];
+            cls_db_group_destroy(g);
+            return fail(rc, m);
+        }
+        *out = g;
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        cls_db_group_destroy(g);
+        return fail(CLS_E_NOMEM, "cls_db_group_create: out of host memory");
+    } catch (const std::exception& ex) {
+        cls_db_group_destroy(g);
+        return fail(CLS_E_INTERNAL, std::string("cls_db_group_create: ") + ex.what());
+    } catch (...) {
+        cls_db_group_destroy(g);
+        return fail(CLS_E_INTERNAL, "cls_db_group_create: unknown exception");
+    }
+}
+
+extern "C" int cls_db_group_size(const cls_db_group* g, uint32_t* n) {
+    if (!g || !n) return fail(CLS_E_INVALID_ARG, "cls_db_group_size: null argument");
+    *n = (uint32_t)g->replicas.size();
+    return CLS_OK;
+}
+
+extern "C" int cls_db_group_replica(cls_db_group* g, uint32_t i, cls_db** db) {
+    if (!g || !db) return fail(CLS_E_INVALID_ARG, "cls_db_group_replica: null argument");
+    if (i >= g->replicas.size()) return fail(CLS_E_INVALID_ARG, "cls_db_group_replica: replica index out of range");
+    *db = g->replicas[i];
+    return CLS_OK;
+}
+
+extern "C" int cls_place_batch_group(cls_db_group* g, const char* bases, const uint64_t* offsets, uint32_t n,
+                                     const cls_params* params, cls_placement* out, cls_query_stats* stats) {
+    if (!g) return fail(CLS_E_INVALID_ARG, "cls_place_batch_group: null handle");
+    if (n == 0) return CLS_OK;
+    int rc = check_host_args(bases, offsets, n, out);
+    if (rc != CLS_OK) return rc;
+    try {
+        // min(G, n) contiguous shards of about equal weight (bases + 1 per read: empty reads count too)
+        const uint32_t n_shards = (uint32_t)std::min<size_t>(g->replicas.size(), n);
+        const unsigned __int128 total = (unsigned __int128)(offsets[n] - offsets[0]) + n;
+        std::vector<uint32_t> cut(n_shards + 1, 0);
+        cut[n_shards] = n;
+        for (uint32_t j = 1; j < n_shards; ++j) {
+            // first read i whose prefix weight (offsets[i] - offsets[0] + i) reaches j / n_shards of the total
+            uint32_t lo = cut[j - 1], hi = n;
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo) / 2;
+                const unsigned __int128 w = (unsigned __int128)(offsets[mid] - offsets[0]) + mid;
+                if (w * n_shards >= total * j) hi = mid; else lo = mid + 1;
+            }
+            cut[j] = lo;
+        }
+        auto shard = [&](uint32_t j) {
+            const uint32_t lo = cut[j];
+            return place_host_checked(g->replicas[j], bases, offsets + lo, cut[j + 1] - lo, params, out + lo, stats ? stats + lo : nullptr);
+        };
+        std::vector<int> rcs(n_shards, CLS_OK);
+        std::vector<std::string> msgs(n_shards);
+        std::vector<std::thread> th;
+        if (n_shards == 1) {  // (one shard: the calling thread places it)
+            rcs[0] = shard(0);
+            if (rcs[0] != CLS_OK) msgs[0] = g_err;
+        } else {
+            try {
+                for (uint32_t j = 0; j < n_shards; ++j) {
+                    if (cut[j] == cut[j + 1]) continue;
+                    th.emplace_back([&, j]() {
+                        try {
+                            rcs[j] = shard(j);
+                            if (rcs[j] != CLS_OK) msgs[j] = g_err;  // (g_err is the worker's own: hand the message back)
+                        } catch (...) {
+                            rcs[j] = CLS_E_INTERNAL;
+                            msgs[j] = "unknown exception";
+                        }
+                    });
+                }
+            } catch (...) {
+                for (auto& t : th) t.join();
+                return fail(CLS_E_INTERNAL, "cls_place_batch_group: could not start a worker thread");
+            }
+        }
+        for (auto& t : th) t.join();
+        for (uint32_t j = 0; j < n_shards; ++j)
+            if (rcs[j] != CLS_OK)
+                return fail(rcs[j], "replica " + std::to_string(j) + " (device " + std::to_string(g->devices[j]) + "): " + msgs[j]);
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CLS_E_NOMEM, "cls_place_batch_group: out of host memory");
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_place_batch_group: unknown exception");
+    }
 }
 
 // FASTA text -> records, all on the device: H2D of the file bytes, cls_fasta_scan_device(), placement straight

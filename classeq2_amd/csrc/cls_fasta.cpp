@@ -108,3 +108,38 @@ extern "C" int cls_fasta_parse(const char* text, size_t len, cls_fasta* out) {
         return CLS_E_INTERNAL;
     }
 }
+
+// One pass over the lines, tracking whether the record open at the current line would be emitted by a '>' line here
+// AND by the end of a piece ending here (the conditions of a safe cut, include/cls_place.h).
+extern "C" int cls_fasta_split(const char* text, size_t len, uint32_t max_pieces, uint64_t* cuts, uint32_t* n_pieces) {
+    if (!cuts || !n_pieces || max_pieces == 0 || (!text && len)) return CLS_E_INVALID_ARG;
+    uint32_t np = 0;
+    cuts[0] = 0;
+    uint32_t next = 1;  // the next interior target: next * len / max_pieces
+    auto target = [&](uint32_t i) { return (uint64_t)((unsigned __int128)i * len / max_pieces); };
+    bool header_ok = false, seq_ok = false;  // of the record the current line belongs to
+    size_t pos = 0;
+    while (pos < len && next < max_pieces) {
+        const char* nl = (const char*)memchr(text + pos, '\n', len - pos);
+        const size_t end = nl ? (size_t)(nl - text) : len;
+        if (text[pos] == '>') {
+            // (an invalid UTF-8 line stops the parse before the record is emitted: no cut at it)
+            if (header_ok && seq_ok && pos >= target(next) && valid_utf8((const unsigned char*)text + pos, end - pos)) {
+                cuts[++np] = pos;
+                while (next < max_pieces && target(next) <= pos) ++next;
+            }
+            header_ok = false;
+            for (size_t i = pos; i < end && !header_ok; ++i) header_ok = text[i] != '>' && text[i] != '\r';
+            seq_ok = false;
+        } else {
+            for (size_t i = pos; i < end && !seq_ok; ++i) {
+                const char c = (char)(text[i] & ~0x20);  // (upper case)
+                seq_ok = c == 'A' || c == 'C' || c == 'G' || c == 'T';
+            }
+        }
+        pos = nl ? end + 1 : len;
+    }
+    cuts[++np] = len;
+    *n_pieces = np;
+    return CLS_OK;
+}

@@ -15,6 +15,7 @@
 #include <charconv>
 #include <chrono>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <map>
 #include <memory>
@@ -693,9 +694,11 @@ extern "C" int cls_serialize_results(const cls_tree* t, const char* headers, con
 
 extern "C" void cls_host_free(void* p) { free(p); }
 
-extern "C" int cls_place_sequences(cls_db* db, const cls_tree* t, const char* query_path, const char* out_file,
-                                   const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds) {
-    if (!db || !t || !query_path || !out_file) return fail(CLS_E_INVALID_ARG, "cls_place_sequences: null argument");
+// The use-case around a placement stage (mod.rs:43-270): output paths and overwrite policy, read the whole input,
+// `place` it (FASTA text -> headers + records), serialise, write.  `who` names the entry in messages.
+using PlaceText = std::function<int(const std::string& text, cls_fasta* fa, cls_placement** recs)>;
+static int place_sequences_with(const char* who, const cls_tree* t, const char* query_path, const char* out_file,
+                                int overwrite, int format, uint32_t* n_placed, double* seconds, const PlaceText& place) {
     // released on every way out, a throwing read_file / serialize_pieces included
     struct Guard {
         FILE *fo = nullptr, *fe = nullptr;
@@ -727,8 +730,8 @@ extern "C" int cls_place_sequences(cls_db* db, const cls_tree* t, const char* qu
         cls_fasta& fa = g.fa;
         cls_placement*& recs = g.recs;  // FASTA stage + placement on the device; headers + records come back
         auto t1 = std::chrono::steady_clock::now();
-        int rc = cls_place_fasta_text(db, text.data(), text.size(), params, &fa, &recs);
-        if (rc != CLS_OK) { std::string m = cls_last_error(); return fail(rc, m); }
+        int rc = place(text, &fa, &recs);
+        if (rc != CLS_OK) return rc;
         std::string().swap(text);
         const bool timing = cls::tuning().timing != 0;
         auto t2 = std::chrono::steady_clock::now();
@@ -747,12 +750,105 @@ extern "C" int cls_place_sequences(cls_db* db, const cls_tree* t, const char* qu
         if (seconds) *seconds = std::chrono::duration<double>(t4 - t0).count();
         if (timing) {
             auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-            fprintf(stderr, "cls_place_sequences: read %.1f ms, fasta+place %.1f ms, serialise %.1f ms, write %.1f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4));
+            fprintf(stderr, "%s: read %.1f ms, fasta+place %.1f ms, serialise %.1f ms, write %.1f ms\n", who, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4));
         }
         return rc;
     } catch (const std::exception& ex) {
-        return fail(CLS_E_INTERNAL, std::string("cls_place_sequences: ") + ex.what());
+        return fail(CLS_E_INTERNAL, std::string(who) + ": " + ex.what());
     } catch (...) {
-        return fail(CLS_E_INTERNAL, "cls_place_sequences: unknown exception");
+        return fail(CLS_E_INTERNAL, std::string(who) + ": unknown exception");
     }
+}
+
+extern "C" int cls_place_sequences(cls_db* db, const cls_tree* t, const char* query_path, const char* out_file,
+                                   const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds) {
+    if (!db || !t || !query_path || !out_file) return fail(CLS_E_INVALID_ARG, "cls_place_sequences: null argument");
+    return place_sequences_with("cls_place_sequences", t, query_path, out_file, overwrite, format, n_placed, seconds,
+                                [&](const std::string& text, cls_fasta* fa, cls_placement** recs) {
+                                    int rc = cls_place_fasta_text(db, text.data(), text.size(), params, fa, recs);
+                                    if (rc != CLS_OK) { std::string m = cls_last_error(); return fail(rc, m); }
+                                    return CLS_OK;
+                                });
+}
+
+// One piece per replica (cls_fasta_split), placed on the replicas' own threads, joined in input order.
+static int place_text_group(cls_db_group* grp, const std::string& text, const cls_params* params, cls_fasta* fa, cls_placement** recs) {
+    uint32_t n_rep = 0;
+    int rc = cls_db_group_size(grp, &n_rep);
+    if (rc != CLS_OK) return fail(rc, cls_last_error());
+    std::vector<uint64_t> cuts((size_t)n_rep + 1);
+    uint32_t n_pieces = 0;
+    rc = cls_fasta_split(text.data(), text.size(), n_rep, cuts.data(), &n_pieces);
+    if (rc != CLS_OK) return fail(rc, "cls_place_sequences_group: cls_fasta_split failed");
+    struct Piece {
+        cls_fasta fa{};
+        cls_placement* recs = nullptr;
+        int rc = CLS_E_INTERNAL;
+        std::string msg = "worker thread not started";
+        Piece() = default;
+        Piece(const Piece&) = delete;
+        ~Piece() { free(recs); cls_fasta_free(&fa); }
+    };
+    std::vector<Piece> pieces(n_pieces);
+    std::vector<int> devices(n_pieces, -1);
+    auto work = [&](uint32_t i) {
+        cls_db* db = nullptr;
+        Piece& p = pieces[i];
+        p.rc = cls_db_group_replica(grp, i, &db);
+        cls_db_info info;
+        if (p.rc == CLS_OK) p.rc = cls_db_info_get(db, &info);
+        if (p.rc == CLS_OK) {
+            devices[i] = info.device;
+            p.rc = cls_place_fasta_text(db, text.data() + cuts[i], cuts[i + 1] - cuts[i], params, &p.fa, &p.recs);
+        }
+        if (p.rc != CLS_OK) p.msg = cls_last_error();  // (the message is the worker's own: hand it back)
+    };
+    if (n_pieces == 1) work(0);
+    else {
+        std::vector<std::thread> th;
+        try {
+            for (uint32_t i = 0; i < n_pieces; ++i) th.emplace_back(work, i);
+        } catch (...) {  // (a piece whose thread could not be started keeps its error)
+        }
+        for (auto& x : th) x.join();
+    }
+    // the parse of the whole text stops where the first piece that stops early does: the pieces after it are dropped
+    uint32_t n_keep = 0;
+    uint64_t n = 0, n_header_bytes = 0;
+    while (n_keep < n_pieces) {
+        const Piece& p = pieces[n_keep++];
+        if (p.rc != CLS_OK)
+            return fail(p.rc, "replica " + std::to_string(n_keep - 1) + " (device " + std::to_string(devices[n_keep - 1]) + "): " + p.msg);
+        n += p.fa.n;
+        n_header_bytes += p.fa.header_off[p.fa.n];
+        if (p.fa.truncated) break;
+    }
+    if (n >= (1ull << 32)) return fail(CLS_E_INVALID_ARG, "cls_place_sequences_group: more than 2^32 - 1 records");
+    memset(fa, 0, sizeof *fa);
+    fa->n = (uint32_t)n;
+    fa->truncated = pieces[n_keep - 1].fa.truncated;
+    fa->headers = (char*)malloc(n_header_bytes + 1);
+    fa->header_off = (uint64_t*)malloc((n + 1) * 8);
+    *recs = (cls_placement*)malloc((n + 1) * sizeof(cls_placement));
+    if (!fa->headers || !fa->header_off || !*recs) return fail(CLS_E_NOMEM, "cls_place_sequences_group: out of host memory");
+    uint64_t r = 0, h = 0;
+    fa->header_off[0] = 0;
+    for (uint32_t i = 0; i < n_keep; ++i) {
+        const cls_fasta& pf = pieces[i].fa;
+        memcpy(fa->headers + h, pf.headers, pf.header_off[pf.n]);
+        for (uint32_t j = 0; j < pf.n; ++j) fa->header_off[r + j + 1] = h + pf.header_off[j + 1];
+        memcpy(*recs + r, pieces[i].recs, (size_t)pf.n * sizeof(cls_placement));
+        h += pf.header_off[pf.n];
+        r += pf.n;
+    }
+    return CLS_OK;
+}
+
+extern "C" int cls_place_sequences_group(cls_db_group* grp, const cls_tree* t, const char* query_path, const char* out_file,
+                                         const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds) {
+    if (!grp || !t || !query_path || !out_file) return fail(CLS_E_INVALID_ARG, "cls_place_sequences_group: null argument");
+    return place_sequences_with("cls_place_sequences_group", t, query_path, out_file, overwrite, format, n_placed, seconds,
+                                [&](const std::string& text, cls_fasta* fa, cls_placement** recs) {
+                                    return place_text_group(grp, text, params, fa, recs);
+                                });
 }

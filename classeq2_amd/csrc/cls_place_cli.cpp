@@ -1,7 +1,7 @@
 // cls-place: C++ look-alike of the reference's `cls place` sub-command
 // (ports/cli/src/cmds/place_sequences.rs:18-82 flag surface, :84-223 behaviour) on the GPU path.
 //   cls-place [QUERY|-] -d DB -o OUT [-a ANNOTATIONS.yaml] [--out-format yaml|jsonl]
-//             [-i N] [-m COV] [-r] [-f] [--device N]
+//             [-i N] [-m COV] [-r] [-f] [--device N[,N...]]
 // The database is read like load_database does (ports/lib/src/functions/load_database.rs:9-53): the `.cls`
 // file of `cls build-db` (zstd-compressed YAML), plain YAML, or the JSON export.
 #include <stdio.h>
@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
 
 #include "cls_host.h"
 
@@ -25,7 +26,8 @@ static void usage() {
             "  -m, --match-coverage <F>            minimum match coverage [default: 0.7]\n"
             "  -r, --remove-intersection           one-vs-rest without the shared k-mers\n"
             "  -f, --force-overwrite               overwrite an existing output file\n"
-            "      --device <N>                    GPU ordinal [default: 0]\n");
+            "      --device <N[,N...]>             GPU ordinal [default: 0]; a comma list places on one replica of the\n"
+            "                                      index per entry (repeats allowed)\n");
 }
 
 int main(int argc, char** argv) {
@@ -33,6 +35,7 @@ int main(int argc, char** argv) {
     cls_params p;
     memset(&p, 0, sizeof p);
     int overwrite = 0, device = 0;
+    std::vector<int> devices;  // --device with a comma: an index group, one replica per entry
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char* name) -> const char* {
@@ -48,7 +51,22 @@ int main(int argc, char** argv) {
         else if (a == "-m" || a == "--match-coverage") { p.flags |= CLS_HAS_MIN_MATCH_COVERAGE; p.min_match_coverage = atof(need("--match-coverage")); }
         else if (a == "-r" || a == "--remove-intersection") { p.flags |= CLS_HAS_REMOVE_INTERSECTION; p.remove_intersection = 1; }
         else if (a == "-f" || a == "--force-overwrite") overwrite = 1;
-        else if (a == "--device") device = atoi(need("--device"));
+        else if (a == "--device") {
+            const std::string v = need("--device");
+            if (v.find(',') == std::string::npos) device = atoi(v.c_str());
+            else {
+                for (size_t p0 = 0; p0 <= v.size();) {
+                    size_t p1 = v.find(',', p0);
+                    if (p1 == std::string::npos) p1 = v.size();
+                    const std::string item = v.substr(p0, p1 - p0);
+                    char* end = nullptr;
+                    const long d = strtol(item.c_str(), &end, 10);
+                    if (item.empty() || *end || d < 0 || d > 1 << 20) { fprintf(stderr, "error: invalid value '%s' for '--device'\n", v.c_str()); return 2; }
+                    devices.push_back((int)d);
+                    p0 = p1 + 1;
+                }
+            }
+        }
         else if (!a.empty() && a[0] == '-' && a != "-") { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); usage(); return 2; }
         else query = a;
     }
@@ -63,14 +81,23 @@ int main(int argc, char** argv) {
     }
     cls_db_desc desc;
     cls_db* db = nullptr;
+    cls_db_group* group = nullptr;
     if (cls_tree_desc(tree, &desc) != CLS_OK) { fprintf(stderr, "%s\n", cls_host_last_error()); return 1; }
-    if (cls_db_create(&desc, device, &db) != CLS_OK) { fprintf(stderr, "%s\n", cls_last_error()); return 1; }
+    if (devices.empty()) {
+        if (cls_db_create(&desc, device, &db) != CLS_OK) { fprintf(stderr, "%s\n", cls_last_error()); return 1; }
+    } else if (cls_db_group_create(&desc, devices.data(), (uint32_t)devices.size(), &group) != CLS_OK) {
+        fprintf(stderr, "%s\n", cls_last_error());
+        return 1;
+    }
     uint32_t n = 0;
     double seconds = 0;
-    int rc = cls_place_sequences(db, tree, query.c_str(), out_path.c_str(), &p, overwrite, fmt == "yaml" ? CLS_FORMAT_YAML : CLS_FORMAT_JSONL, &n, &seconds);
+    const int format = fmt == "yaml" ? CLS_FORMAT_YAML : CLS_FORMAT_JSONL;
+    int rc = db ? cls_place_sequences(db, tree, query.c_str(), out_path.c_str(), &p, overwrite, format, &n, &seconds)
+                : cls_place_sequences_group(group, tree, query.c_str(), out_path.c_str(), &p, overwrite, format, &n, &seconds);
     if (rc != CLS_OK) fprintf(stderr, "%s\n", cls_host_last_error());
     else fprintf(stderr, "{\"code\":\"CLIPLACE0002\",\"sequences\":%u,\"totalSeconds\":%.6f,\"averageSeconds\":%.9f}\n", n, seconds, n ? seconds / n : 0.0);
     cls_db_destroy(db);
+    cls_db_group_destroy(group);
     cls_tree_free(tree);
     return rc == CLS_OK ? 0 : 1;
 }

@@ -24,13 +24,14 @@ _LIB = None
 EXPORTS = [
     "cls_device_count", "cls_db_create", "cls_db_validate", "cls_db_destroy", "cls_db_info_get", "cls_db_info_get2", "cls_db_kernel_time", "cls_db_kernel_name",
     "cls_db_read_classes", "cls_db_set_max_read_len", "cls_place_batch",
+    "cls_db_group_create", "cls_db_group_destroy", "cls_db_group_size", "cls_db_group_replica", "cls_place_batch_group", "cls_fasta_split",
     "cls_place_batch_device", "cls_place_batch_stats", "cls_fasta_parse", "cls_fasta_free", "cls_fasta_scan_device", "cls_fasta_dev_free",
     "cls_fasta_parse_gpu", "cls_place_fasta_text", "cls_last_error",
     "cls_version", "cls_set_tuning", "cls_tuning_from_env",
 ]
 HOST_EXPORTS = [
     "cls_tree_load_json", "cls_tree_load", "cls_tree_init_from_file", "cls_tree_from_newick", "cls_tree_serialize", "cls_tree_save", "cls_tree_free", "cls_tree_set_annotations_yaml", "cls_tree_build_kmers_map", "cls_tree_desc", "cls_serialize_results",
-    "cls_host_free", "cls_place_sequences", "cls_host_last_error",
+    "cls_host_free", "cls_place_sequences", "cls_place_sequences_group", "cls_host_last_error",
 ]
 SERVICE_EXPORTS = [
     "cls_service_create", "cls_service_destroy", "cls_service_add_model", "cls_service_submit", "cls_service_wait", "cls_service_pause",
@@ -80,6 +81,18 @@ def lib():
         L.cls_place_batch_stats.restype = i32
         L.cls_place_batch_device.argtypes = [vp, vp, vp, u32, C.POINTER(_abi.Params), vp, vp, vp]
         L.cls_place_batch_device.restype = i32
+        L.cls_db_group_create.argtypes = [C.POINTER(_abi.DbDesc), C.POINTER(i32), u32, C.POINTER(vp)]
+        L.cls_db_group_create.restype = i32
+        L.cls_db_group_destroy.argtypes = [vp]
+        L.cls_db_group_destroy.restype = None
+        L.cls_db_group_size.argtypes = [vp, C.POINTER(u32)]
+        L.cls_db_group_size.restype = i32
+        L.cls_db_group_replica.argtypes = [vp, u32, C.POINTER(vp)]
+        L.cls_db_group_replica.restype = i32
+        L.cls_place_batch_group.argtypes = [vp, vp, vp, u32, C.POINTER(_abi.Params), vp, vp]
+        L.cls_place_batch_group.restype = i32
+        L.cls_fasta_split.argtypes = [C.c_char_p, C.c_size_t, u32, C.POINTER(C.c_uint64), C.POINTER(u32)]
+        L.cls_fasta_split.restype = i32
         L.cls_fasta_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_abi.Fasta)]
         L.cls_fasta_parse.restype = i32
         L.cls_fasta_parse_gpu.argtypes = [C.c_char_p, C.c_size_t, i32, C.POINTER(_abi.Fasta)]
@@ -123,6 +136,9 @@ def lib():
         L.cls_place_sequences.argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.POINTER(_abi.Params), i32, i32,
                                           C.POINTER(u32), C.POINTER(C.c_double)]
         L.cls_place_sequences.restype = i32
+        L.cls_place_sequences_group.argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.POINTER(_abi.Params), i32, i32,
+                                                C.POINTER(u32), C.POINTER(C.c_double)]
+        L.cls_place_sequences_group.restype = i32
         L.cls_host_last_error.restype = C.c_char_p
         # resident batching service (include/cls_service.h)
         L.cls_service_create.argtypes = [C.POINTER(vp)]
@@ -201,6 +217,14 @@ def fasta_parse(text: bytes, device: Optional[int] = None):
         return headers, bases, boff, bool(f.truncated)
     finally:
         lib().cls_fasta_free(C.byref(f))
+
+
+def fasta_split(text: bytes, max_pieces: int) -> list:
+    """Cut points for parsing `text` in up to `max_pieces` pieces (cls_fasta_split): [0, ..., len(text)]."""
+    cuts = (C.c_uint64 * (max_pieces + 1))()
+    n = C.c_uint32(0)
+    _check(lib().cls_fasta_split(text, len(text), max_pieces, cuts, C.byref(n)))
+    return [int(c) for c in cuts[: n.value + 1]]
 
 
 class PlacementDb:
@@ -307,6 +331,71 @@ class PlacementDb:
         _check(lib().cls_place_batch_device(self._h, d_bases, d_offsets, n, pp, d_out, d_stats or None, stream or None))
 
 
+class _ReplicaView(PlacementDb):
+    """Non-owning PlacementDb on one replica of a PlacementDbGroup (cls_db_group_replica); keeps the group alive."""
+
+    def __init__(self, group: "PlacementDbGroup", handle: C.c_void_p):
+        self._group = group
+        self._h = handle
+        self.info = _abi.DbInfo()
+        _check(lib().cls_db_info_get(self._h, C.byref(self.info)))
+
+    def close(self):
+        self._h = C.c_void_p()  # (the group owns the handle)
+
+
+class PlacementDbGroup:
+    """Owned group of replicas of one index (cls_db_group): encoded once, one replica per entry of `devices`
+    (repeats allowed; None: every visible device once).  place_batch cuts a batch across the replicas."""
+
+    def __init__(self, flat: FlatDb, devices=None):
+        self._h = C.c_void_p()
+        d = flat.desc()
+        devs = list(devices) if devices is not None else []
+        arr = (C.c_int * len(devs))(*devs) if devs else None
+        _check(lib().cls_db_group_create(C.byref(d), arr, len(devs), C.byref(self._h)))
+        n = C.c_uint32(0)
+        _check(lib().cls_db_group_size(self._h, C.byref(n)))
+        self.size = n.value
+
+    def replica(self, i: int) -> PlacementDb:
+        """Replica i as a PlacementDb view; closing or dropping the view leaves the replica to the group."""
+        h = C.c_void_p()
+        _check(lib().cls_db_group_replica(self._h, i, C.byref(h)))
+        return _ReplicaView(self, h)
+
+    def place_batch(self, bases: np.ndarray, offsets: np.ndarray, params: Optional[_abi.Params] = None,
+                    want_stats: bool = False):
+        """Host buffers in, host records out, across the replicas (cls_place_batch_group)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        out = np.zeros(n, dtype=_abi.PLACEMENT_DTYPE)
+        stats = np.zeros(n, dtype=_abi.STATS_DTYPE) if want_stats else None
+        pp = C.byref(params) if params is not None else None
+        _check(lib().cls_place_batch_group(self._h, bases.ctypes.data, offsets.ctypes.data, n, pp, out.ctypes.data,
+                                           stats.ctypes.data if want_stats else None))
+        return (out, stats) if want_stats else out
+
+    def close(self):
+        """Frees every replica: views from replica() must not be used afterwards."""
+        if getattr(self, "_h", None):
+            lib().cls_db_group_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def _check_host(rc: int):
     if rc != 0:
         msg = lib().cls_host_last_error().decode(errors="replace") or lib().cls_last_error().decode(errors="replace")
@@ -391,11 +480,13 @@ class Tree:
             lib().cls_host_free(err)
 
 
-def place_sequences(db: "PlacementDb", tree: Tree, query_path: str, out_file: str, params: Optional[_abi.Params] = None,
+def place_sequences(db, tree: Tree, query_path: str, out_file: str, params: Optional[_abi.Params] = None,
                     overwrite: bool = False, fmt: int = FORMAT_YAML):
-    """The whole use-case (mod.rs:43-270) through cls_place_sequences: -> (records read, seconds)."""
+    """The whole use-case (mod.rs:43-270) through cls_place_sequences, or cls_place_sequences_group when `db` is a
+    PlacementDbGroup: -> (records read, seconds)."""
     n, sec = C.c_uint32(0), C.c_double(0)
-    _check_host(lib().cls_place_sequences(db._h, tree._h, query_path.encode(), out_file.encode(),
+    fn = lib().cls_place_sequences_group if isinstance(db, PlacementDbGroup) else lib().cls_place_sequences
+    _check_host(fn(db._h, tree._h, query_path.encode(), out_file.encode(),
                                           C.byref(params) if params is not None else None, 1 if overwrite else 0, fmt,
                                           C.byref(n), C.byref(sec)))
     return n.value, sec.value

@@ -71,6 +71,12 @@ void cls_host_free(void* p);
  * `--force-overwrite`.  Returns the number of records read and the UCPLACE0001->0002 wall time. */
 int cls_place_sequences(cls_db* db, const cls_tree* t, const char* query_path, const char* out_file,
                         const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds);
+/* The same use-case on an index group: the text is cut with cls_fasta_split into one piece per replica, each
+ * replica runs cls_place_fasta_text on its piece on a host thread of its own, and the pieces' headers and records are
+ * joined in input order (up to the first piece that stops early) before the output stage.  The files are
+ * byte-identical to those of cls_place_sequences on one handle. */
+int cls_place_sequences_group(cls_db_group* g, const cls_tree* t, const char* query_path, const char* out_file,
+                              const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds);
 
 const char* cls_host_last_error(void);
 

@@ -268,6 +268,28 @@ int cls_db_read_classes(const cls_db* db, uint64_t n_bases, int stats, cls_read_
 int cls_place_batch_stats(cls_db* db, const char* bases, const uint64_t* offsets, uint32_t n,
                           const cls_params* params, cls_placement* out, cls_query_stats* stats);
 
+/* ---- index groups: one index on several devices, one process --------------
+ * N replicas of one index, each a cls_db of its own.  The descriptor is validated and re-encoded once on the
+ * host (the costly half of cls_db_create) and uploaded to every replica in parallel, one host thread each.
+ * `devices` lists one ordinal per replica; repeats are allowed ({0, 0}: two replicas on device 0).  NULL or
+ * n_devices == 0: every visible device, once each.  Every ordinal is checked before the encoding: out of range is
+ * CLS_E_INVALID_ARG; no device at all is CLS_E_NO_DEVICE.  When an upload fails every replica is freed and the error
+ * names the replica and its device. */
+typedef struct cls_db_group cls_db_group;   /* opaque; N replicas of one index */
+int cls_db_group_create(const cls_db_desc* d, const int* devices, uint32_t n_devices, cls_db_group** out);
+void cls_db_group_destroy(cls_db_group* g);
+int cls_db_group_size(const cls_db_group* g, uint32_t* n);
+/* Replica i as a cls_db for every per-handle entry (info, kernel time, device-buffer batches).  Borrowed: it lives
+ * as long as the group; never cls_db_destroy it. */
+int cls_db_group_replica(cls_db_group* g, uint32_t i, cls_db** db);
+/* cls_place_batch / cls_place_batch_stats across the group: host buffers, synchronous, `out[n]` (and `stats[n]`,
+ * may be NULL) in input order, re-entrant.  The batch is cut into min(N, n) contiguous shards of about equal weight
+ * (bases + 1 per read); replica i places shard i on a host thread of its own (one shard: on the calling thread),
+ * straight into the caller's buffers.  Waits for every shard; the error of the lowest failing shard is returned,
+ * its message prefixed "replica i (device d): ".  Records and counters equal those of cls_place_batch on one handle. */
+int cls_place_batch_group(cls_db_group* g, const char* bases, const uint64_t* offsets, uint32_t n,
+                          const cls_params* params, cls_placement* out, cls_query_stats* stats);
+
 /* ---- FASTA input stage (file_or_stdin.rs:76-116, sequence.rs:47-56) ------ */
 typedef struct cls_fasta {
     uint32_t n;               /* records                                        */
@@ -280,6 +302,14 @@ typedef struct cls_fasta {
 
 int cls_fasta_parse(const char* text, size_t len, cls_fasta* out);
 void cls_fasta_free(cls_fasta* f);
+/* Host only: cut points for parsing `text` in up to `max_pieces` pieces, one cls_fasta_parse (or device FASTA stage)
+ * each.  cuts[0] = 0 <= cuts[1] < ... < cuts[*n_pieces] = len (`cuts` holds max_pieces + 1 entries).  Interior cut i is
+ * the first safe cut at or after i * len / max_pieces (duplicates dropped).  A safe cut starts a '>' line that is
+ * valid UTF-8 and ends a record whose header line is not empty once '\r' and every '>' are removed and whose sequence
+ * lines hold one of ACGTacgt: the parse of the whole text emits that record there, the parse of the piece emits it at
+ * its end, and the next piece starts in the parser's initial state.  Concatenating the pieces' records, up to and including the first
+ * piece that reports `truncated` (the pieces after it are dropped), gives the records of the whole text. */
+int cls_fasta_split(const char* text, size_t len, uint32_t max_pieces, uint64_t* cuts, uint32_t* n_pieces);
 
 /* The same stage as data-parallel passes on the device: `d_text` = the file's bytes in HBM; the filtered bases
  * and their offsets stay in HBM, ready for cls_place_batch_device() (the reads never return to the host); the
