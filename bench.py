@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: query placements/sec on the 10k-leaf tree, 150 bp reads.
 
-    python bench.py --gpus N --steps K --warmup W [--config C3] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config C3] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the placement hot path (`cls_place_batch_device`, the
 C-ABI entry a Rust caller would bind) over one batch of synthetic reads that is
@@ -19,7 +19,10 @@ support-collapsed 10k-leaf tree at k=12 and at the reference's default k=35), G3
 support-collapsed tree, k=35, m=4).
 
 Rank 0 prints ONE JSON line; DESIGN.md "Measurement" says how `roofline`,
-`host_window` and `cpu_baseline` are obtained.
+`host_window` and `cpu_baseline` are obtained.  A plain run sets up (index, reads, one untimed statistics pass whose
+records the timed steps must reproduce), warms up, times the steps, dumps what it is asked to and prints the line;
+`--full` adds what the headline does not need: the host-buffer window and the CPU baseline with its parity check
+against the GPU records (N=1 only, tens of seconds).
 """
 import argparse
 import hashlib
@@ -245,8 +248,11 @@ def main():
                     "mod.rs:64-67 / 264-267), JSONL and YAML, on this config's reads")
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU (default: the config's; C4: total reads of the stream)")
     ap.add_argument("--scale", type=float, default=1.0, help="C5 only: fraction of the 50k leaves / 1M reads to run")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-window", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need (N=1): "
+                    "`host_window` (cls_place_batch, host buffers) and `cpu_baseline` (the C oracle on this host's cores, its "
+                    "records compared with the GPU's: `parity_checked_reads`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out `cpu_baseline`")
+    ap.add_argument("--no-host-window", action="store_true", help="with --full: leave out `host_window`")
     ap.add_argument("--dump-records", default="", help="rank 0 writes the records it holds after the last step (all ranks' "
                     "shards in rank order at N > 1) to this .npy file: lets a test check the gathered records against the oracle")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes the records of the last timed step (all "
@@ -457,7 +463,7 @@ def main():
             "dtype": "u64",
             "data": "synthetic" + (" (REHEARSAL: all ranks on one GPU, gloo; not a measurement)" if rehearsal else ""),
             "window": "device-resident: reads in HBM -> records in HBM (cls_place_batch_device, every kernel of the call"
-                      + (" + the gather to rank 0" if world > 1 else "") + "); the host-buffer window is `host_window`",
+                      + (" + the gather to rank 0" if world > 1 else "") + "); the host-buffer window is `host_window` (--full)",
             "config": {
                 "workload": f"{args.config}: {cfg['n_leaves']}-leaf {'deep (depth <= %d) ' % cfg['max_depth'] if cfg['deep'] else ''}"
                             f"{'support-collapsed ' if cfg.get('collapse_prob') else ''}tree, "
@@ -517,14 +523,14 @@ def main():
                 line["config"]["dumped_records"] = int(len(allrec))
             if args.dump_outputs:
                 line["config"]["dumped_outputs"] = {"rows": dump_outputs(args.dump_outputs, allrec), "of": int(len(allrec))}
-        if not args.no_host_window and world == 1 and mine:
+        if args.full and not args.no_host_window and world == 1 and mine:
             hw, host_recs = host_window(db, bases, offsets, mine)
             for f in ("status", "one", "rest", "levels", "clade_id"):
                 assert (host_recs[f] == ref_out[f][:mine]).all(), "host-buffer entry disagrees with the device-buffer entry"
             line["host_window"] = hw
         if args.e2e and world == 1 and mine:
             line["e2e"] = e2e_window(db, synth, cfg, bases, mine)
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             cb, oracle_recs = cpu_baseline(synth, cfg, first)
             n_chk = min(len(oracle_recs), mine)
             for f in ("status", "one", "rest", "levels", "clade_id"):

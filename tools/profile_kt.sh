@@ -1,5 +1,5 @@
 #!/bin/bash
-# Kernel-trace profile of one bench configuration (no PMC passes): rocprofv3 kernel stats + the plain bench line.
+# Kernel-trace profile of one bench configuration (no PMC passes): rocprofv3 kernel stats + the --full bench line.
 # usage: bash tools/profile_kt.sh <tag> <config> [extra bench args]   -> gpurun_out/<tag>/<config>_{kernel_stats.csv,bench.json}
 set -e
 TAG=$1; CFG=$2; shift; shift
@@ -10,7 +10,7 @@ BENCH="python3 $PWD/bench.py --config $CFG $*"
 cd /tmp
 timeout -k 10 900 rocprofv3 --kernel-trace --stats -d "$OUT/kt_$CFG" -o kt --output-format csv -- $BENCH --no-cpu-baseline --no-host-window > "$OUT/${CFG}_bench_kt.json" 2> "$OUT/${CFG}_kt.err"
 cd - > /dev/null
-timeout -k 10 900 $BENCH > "$OUT/${CFG}_bench.json" 2> "$OUT/${CFG}_bench.err"
+timeout -k 10 900 $BENCH --full > "$OUT/${CFG}_bench.json" 2> "$OUT/${CFG}_bench.err"
 python3 - "$OUT" "$CFG" <<'PY'
 import csv, glob, re, sys
 out, cfg = sys.argv[1], sys.argv[2]
