@@ -74,6 +74,44 @@ class DbDesc(C.Structure):
     ]
 
 
+BUILD_REFERENCE_HEADER_SHIFT, BUILD_FORWARD_ONLY, BUILD_LEAVES_ONLY = 1, 2, 4
+
+
+class BuildDesc(C.Structure):
+    """cls_build_desc (cls_kmers_build)."""
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("n_nodes", C.c_uint32),
+        ("nodes", C.POINTER(Node)),
+        ("k_size", C.c_uint64),
+        ("m_size", C.c_uint64),
+        ("n_records", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("bases", C.c_void_p),
+        ("offsets", C.POINTER(C.c_uint64)),
+        ("leaf_id", C.POINTER(C.c_uint64)),
+    ]
+
+
+class KmersInfo(C.Structure):
+    """cls_kmers_info."""
+    _fields_ = [
+        ("n_windows", C.c_uint64),
+        ("n_kmers", C.c_uint64),
+        ("n_leaf_postings", C.c_uint64),
+        ("n_node_ids", C.c_uint64),
+        ("n_buckets", C.c_uint64),
+        ("peak_device_bytes", C.c_uint64),
+        ("ms_hash", C.c_double),
+        ("ms_sort", C.c_double),
+        ("ms_group", C.c_double),
+        ("ms_d2h", C.c_double),
+        ("ms_expand", C.c_double),
+        ("sort_passes", C.c_uint32),
+        ("full_key", C.c_uint32),
+    ]
+
+
 class Params(C.Structure):
     _fields_ = [
         ("flags", C.c_uint32),
@@ -183,6 +221,7 @@ assert C.sizeof(Node) == 32
 assert C.sizeof(Placement) == 24
 assert C.sizeof(QueryStats) == 24
 assert C.sizeof(Params) == 24
+assert C.sizeof(BuildDesc) == 64 and C.sizeof(KmersInfo) == 96
 
 import numpy as np  # noqa: E402
 

@@ -126,6 +126,7 @@ const Knob KNOBS[] = {
     {"order_windows", &cls::Tuning::order_windows}, {"order_both_strands", &cls::Tuning::order_both_strands},
     {"order_block_shift", &cls::Tuning::order_block_shift}, {"order_sample_shift", &cls::Tuning::order_sample_shift},
     {"profile_stop", &cls::Tuning::profile_stop}, {"timing", &cls::Tuning::timing},
+    {"build_full_key", &cls::Tuning::build_full_key},
 };
 }  // namespace
 

@@ -511,8 +511,9 @@ void cls_tree_visit_leaves(const cls_tree* t, const std::function<void(const cha
 
 void cls_tree_set_kmers_map(cls_tree* t, uint64_t k, uint64_t m, std::vector<uint64_t>&& bucket_key,
                             std::vector<uint64_t>&& bucket_kmer_off, std::vector<uint64_t>&& kmer_hash,
-                            std::vector<uint64_t>&& kmer_node_off, std::vector<uint64_t>&& node_ids) {
+                            std::vector<uint64_t>&& kmer_node_off, std::vector<uint64_t>&& node_ids, uint32_t node_set_kind) {
     t->has_kmers = true;
+    t->node_set_kind = node_set_kind;
     t->k_size = k;
     t->m_size = m;
     t->bucket_key = std::move(bucket_key);
@@ -633,6 +634,7 @@ extern "C" int cls_tree_desc(const cls_tree* t, cls_db_desc* d) {
     d->kmer_hash = t->kmer_hash.data();
     d->kmer_node_off = t->kmer_node_off.data();
     d->node_ids = t->node_ids.data();
+    d->node_set_kind = t->node_set_kind;
     return CLS_OK;
 }
 

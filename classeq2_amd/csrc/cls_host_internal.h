@@ -52,6 +52,7 @@ struct cls_tree {
     // k-mer map (optional)
     bool has_kmers = false;
     uint64_t k_size = 0, m_size = 0;
+    uint32_t node_set_kind = CLS_SETS_EXPLICIT;  // CLS_SETS_LEAVES only after a CLS_BUILD_LEAVES_ONLY build (never serialised)
     std::vector<uint64_t> bucket_key, bucket_kmer_off, kmer_hash, kmer_node_off, node_ids;
 };
 
@@ -66,4 +67,5 @@ int cls_host_fail(int code, const std::string& msg);
 void cls_tree_visit_leaves(const cls_tree* t, const std::function<void(const char*, const std::vector<uint64_t>&)>& fn);
 void cls_tree_set_kmers_map(cls_tree* t, uint64_t k, uint64_t m, std::vector<uint64_t>&& bucket_key,
                             std::vector<uint64_t>&& bucket_kmer_off, std::vector<uint64_t>&& kmer_hash,
-                            std::vector<uint64_t>&& kmer_node_off, std::vector<uint64_t>&& node_ids);
+                            std::vector<uint64_t>&& kmer_node_off, std::vector<uint64_t>&& node_ids,
+                            uint32_t node_set_kind = CLS_SETS_EXPLICIT);

@@ -678,6 +678,9 @@ extern "C" int cls_tree_load(const char* path, cls_tree** out) {
 
 extern "C" int cls_tree_serialize(const cls_tree* t, int format, int only_tree, char** out, size_t* out_len) {
     if (!t || !out || !out_len) return cls_host_fail(CLS_E_INVALID_ARG, "cls_tree_serialize: null argument");
+    if (!only_tree && t->has_kmers && t->node_set_kind != CLS_SETS_EXPLICIT)
+        return cls_host_fail(CLS_E_INVALID_ARG, "cls_tree_serialize: the k-mer map holds leaves-only node sets (CLS_BUILD_LEAVES_ONLY); "
+                                                "the database format holds explicit sets: build without it, or write only_tree");
     try {
         std::string s;
         if (format == CLS_DB_FORMAT_JSON) s = tree_json(t, only_tree != 0);

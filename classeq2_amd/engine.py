@@ -27,10 +27,10 @@ EXPORTS = [
     "cls_db_group_create", "cls_db_group_destroy", "cls_db_group_size", "cls_db_group_replica", "cls_place_batch_group", "cls_fasta_split",
     "cls_place_batch_device", "cls_place_batch_stats", "cls_fasta_parse", "cls_fasta_free", "cls_fasta_scan_device", "cls_fasta_dev_free",
     "cls_fasta_parse_gpu", "cls_place_fasta_text", "cls_last_error",
-    "cls_version", "cls_set_tuning", "cls_tuning_from_env",
+    "cls_version", "cls_set_tuning", "cls_tuning_from_env", "cls_kmers_build", "cls_kmers_desc", "cls_kmers_info_get", "cls_kmers_free",
 ]
 HOST_EXPORTS = [
-    "cls_tree_load_json", "cls_tree_load", "cls_tree_init_from_file", "cls_tree_from_newick", "cls_tree_serialize", "cls_tree_save", "cls_tree_free", "cls_tree_set_annotations_yaml", "cls_tree_build_kmers_map", "cls_tree_desc", "cls_serialize_results",
+    "cls_tree_load_json", "cls_tree_load", "cls_tree_init_from_file", "cls_tree_from_newick", "cls_tree_serialize", "cls_tree_save", "cls_tree_free", "cls_tree_set_annotations_yaml", "cls_tree_build_kmers_map", "cls_tree_build_kmers_map_device", "cls_tree_desc", "cls_serialize_results",
     "cls_host_free", "cls_place_sequences", "cls_place_sequences_group", "cls_host_last_error",
 ]
 SERVICE_EXPORTS = [
@@ -107,6 +107,14 @@ def lib():
         L.cls_set_tuning.restype = i32
         L.cls_tuning_from_env.argtypes = []
         L.cls_tuning_from_env.restype = None
+        L.cls_kmers_build.argtypes = [C.POINTER(_abi.BuildDesc), i32, C.POINTER(vp)]
+        L.cls_kmers_build.restype = i32
+        L.cls_kmers_desc.argtypes = [vp, C.POINTER(_abi.BuildDesc), C.POINTER(_abi.DbDesc)]
+        L.cls_kmers_desc.restype = i32
+        L.cls_kmers_info_get.argtypes = [vp, C.POINTER(_abi.KmersInfo)]
+        L.cls_kmers_info_get.restype = i32
+        L.cls_kmers_free.argtypes = [vp]
+        L.cls_kmers_free.restype = None
         # host-side mirror (include/cls_host.h)
         L.cls_tree_load_json.argtypes = [C.c_char_p, C.POINTER(vp)]
         L.cls_tree_load_json.restype = i32
@@ -126,6 +134,8 @@ def lib():
         L.cls_tree_set_annotations_yaml.restype = i32
         L.cls_tree_build_kmers_map.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_uint64, C.c_uint64, u32]
         L.cls_tree_build_kmers_map.restype = i32
+        L.cls_tree_build_kmers_map_device.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_uint64, C.c_uint64, u32, i32]
+        L.cls_tree_build_kmers_map_device.restype = i32
         L.cls_tree_desc.argtypes = [vp, C.POINTER(_abi.DbDesc)]
         L.cls_tree_desc.restype = i32
         L.cls_serialize_results.argtypes = [vp, C.c_char_p, vp, u32, vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t),
@@ -217,6 +227,42 @@ def fasta_parse(text: bytes, device: Optional[int] = None):
         return headers, bases, boff, bool(f.truncated)
     finally:
         lib().cls_fasta_free(C.byref(f))
+
+
+def build_kmers(nodes: np.ndarray, bases: np.ndarray, offsets: np.ndarray, leaf_ids: np.ndarray, k: int, m: int, *,
+                leaves_only: bool = False, forward_only: bool = False, device: int = 0, return_info: bool = False):
+    """The k-mer index of `nodes` (NODE_DTYPE rows) built on the GPU from records `bases[offsets[i]:offsets[i+1]]`
+    (filtered upper-case ACGT), record i filed under the LEAF clade `leaf_ids[i]` (cls_kmers_build) -> FlatDb in
+    canonical order; with `return_info`, (FlatDb, dict of cls_kmers_info)."""
+    nodes = np.ascontiguousarray(nodes, dtype=_abi.NODE_DTYPE)
+    bases = np.ascontiguousarray(np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray)) else bases, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    leaf_ids = np.ascontiguousarray(leaf_ids, dtype=np.uint64)
+    if len(offsets) != len(leaf_ids) + 1:
+        raise ValueError("offsets must hold one entry more than leaf_ids")
+    b = _abi.BuildDesc()
+    b.abi_version = _abi.ABI_VERSION
+    b.n_nodes = len(nodes)
+    b.nodes = nodes.ctypes.data_as(C.POINTER(_abi.Node))
+    b.k_size, b.m_size = k, m
+    b.n_records = len(leaf_ids)
+    b.flags = (_abi.BUILD_LEAVES_ONLY if leaves_only else 0) | (_abi.BUILD_FORWARD_ONLY if forward_only else 0)
+    b.bases = bases.ctypes.data
+    b.offsets = offsets.ctypes.data_as(C.POINTER(C.c_uint64))
+    b.leaf_id = leaf_ids.ctypes.data_as(C.POINTER(C.c_uint64))
+    km = C.c_void_p()
+    _check(lib().cls_kmers_build(C.byref(b), device, C.byref(km)))
+    try:
+        d = _abi.DbDesc()
+        _check(lib().cls_kmers_desc(km, C.byref(b), C.byref(d)))
+        flat = FlatDb.from_desc(d, copy=True)
+        inf = _abi.KmersInfo()
+        _check(lib().cls_kmers_info_get(km, C.byref(inf)))
+    finally:
+        lib().cls_kmers_free(km)
+    if return_info:
+        return flat, {name: getattr(inf, name) for name, _ in _abi.KmersInfo._fields_}
+    return flat
 
 
 def fasta_split(text: bytes, max_pieces: int) -> list:
@@ -458,6 +504,14 @@ class Tree:
         """`cls build-db` (map_kmers_to_tree) on this tree; see include/cls_host.h."""
         flags = (1 if reference_header_shift else 0) | (2 if forward_only else 0)
         _check_host(lib().cls_tree_build_kmers_map(self._h, msa_text, len(msa_text), k_size, m_size, flags))
+
+    def build_kmers_map_device(self, msa_text: bytes, k_size: int, m_size: int = 4, reference_header_shift: bool = True,
+                               forward_only: bool = False, device: int = 0, leaves_only: bool = False) -> None:
+        """The same map built on the GPU (cls_tree_build_kmers_map_device); `leaves_only` keeps it as CLS_SETS_LEAVES
+        (then `dumps` / `save` need only_tree)."""
+        flags = ((_abi.BUILD_REFERENCE_HEADER_SHIFT if reference_header_shift else 0) | (_abi.BUILD_FORWARD_ONLY if forward_only else 0)
+                 | (_abi.BUILD_LEAVES_ONLY if leaves_only else 0))
+        _check_host(lib().cls_tree_build_kmers_map_device(self._h, msa_text, len(msa_text), k_size, m_size, flags, device))
 
     def flat(self) -> FlatDb:
         d = _abi.DbDesc()

@@ -51,9 +51,16 @@ int cls_tree_set_annotations_yaml(cls_tree* t, const char* path);
  * `msa_text` is the multi-FASTA whose headers name the tree's leaves.  Replaces the tree's k-mer map. */
 #define CLS_BUILD_REFERENCE_HEADER_SHIFT 1u /* file record i's k-mers under header i+1, never index the last record
                                              * (what the reference does, build_database/mod.rs:93-116) */
-#define CLS_BUILD_FORWARD_ONLY 2u           /* forward k-mers only (builds older than the reverse-complement change) */
+/* CLS_BUILD_FORWARD_ONLY, CLS_BUILD_LEAVES_ONLY: cls_place.h.  With CLS_BUILD_LEAVES_ONLY the tree keeps the map as
+ * CLS_SETS_LEAVES (cls_tree_desc reports it); the reference's file format holds explicit sets, so cls_tree_serialize
+ * and cls_tree_save then refuse unless `only_tree`. */
 int cls_tree_build_kmers_map(cls_tree* t, const char* msa_text, size_t msa_len, uint64_t k_size, uint64_t m_size,
                              uint32_t flags);
+/* The same on the GPU `device` (-1: the current one): the MSA text goes through the device FASTA stage, only its
+ * headers come back to be matched to leaves (as above, same errors), and cls_kmers_build makes the map.  The map is
+ * byte for byte the one cls_tree_build_kmers_map makes.  k_size at most 1024. */
+int cls_tree_build_kmers_map_device(cls_tree* t, const char* msa_text, size_t msa_len, uint64_t k_size, uint64_t m_size,
+                                    uint32_t flags, int device);
 /* Borrowed flat view for cls_db_create(); valid while `t` lives. */
 int cls_tree_desc(const cls_tree* t, cls_db_desc* d);
 

@@ -290,6 +290,59 @@ int cls_db_group_replica(cls_db_group* g, uint32_t i, cls_db** db);
 int cls_place_batch_group(cls_db_group* g, const char* bases, const uint64_t* offsets, uint32_t n,
                           const cls_params* params, cls_placement* out, cls_query_stats* stats);
 
+/* ---- index builder: map_kmers_to_tree (core/src/use_cases/build_database/mod.rs:26-181) on the device ----------
+ * Records (filtered bases, one LEAF clade each) -> the k-mer map of cls_db_desc, without a cls_tree (cls_host.h has the
+ * Newick + MSA use-case above it).  Every window of k bases of a record gives its forward k-mer and its reverse
+ * complement (kmers_map.rs:375-398); a record shorter than k gives none.  k-mer hash = murmur3_x64_128(k-mer, 0).0,
+ * bucket key = the same of its first min(m, k) characters, 0 when m = 0 (kmers_map.rs:125-149).  The result is in
+ * canonical order: buckets ascending by key, k-mers ascending by hash inside a bucket, ids ascending inside a k-mer --
+ * byte for byte what the host builder (cls_tree_build_kmers_map) makes of the same records. */
+#define CLS_BUILD_FORWARD_ONLY 2u /* forward k-mers only (builds older than the reverse-complement change)           */
+#define CLS_BUILD_LEAVES_ONLY 4u  /* node sets as CLS_SETS_LEAVES (the distinct leaves of each k-mer), not explicit  */
+
+typedef struct cls_build_desc {
+    uint32_t abi_version;       /* CLS_ABI_VERSION                                                              */
+    uint32_t n_nodes;
+    const cls_node* nodes;      /* the tree exactly as cls_db_create takes it                                   */
+    uint64_t k_size;            /* [1, 1024]                                                                    */
+    uint64_t m_size;
+    uint32_t n_records;
+    uint32_t flags;             /* CLS_BUILD_FORWARD_ONLY | CLS_BUILD_LEAVES_ONLY                               */
+    const char* bases;          /* host memory: concatenated records (filtered upper-case ACGT)                 */
+    const uint64_t* offsets;    /* [n_records + 1] non-decreasing byte offsets into `bases`                     */
+    const uint64_t* leaf_id;    /* [n_records] id of the childless LEAF-kind clade each record is filed under   */
+} cls_build_desc;
+
+typedef struct cls_kmers cls_kmers; /* owned result of a build */
+
+/* Measurement aid: sizes and device times (HIP events) of one build. */
+typedef struct cls_kmers_info {
+    uint64_t n_windows;         /* k-mer occurrences hashed (both strands)                                      */
+    uint64_t n_kmers;           /* distinct (bucket, hash)                                                      */
+    uint64_t n_leaf_postings;   /* distinct (k-mer, leaf) pairs                                                 */
+    uint64_t n_node_ids;        /* ids of the result (= n_leaf_postings for CLS_BUILD_LEAVES_ONLY)             */
+    uint64_t n_buckets;
+    uint64_t peak_device_bytes; /* device memory the build held at its peak (input bases included)             */
+    double ms_hash;             /* H2D of the records' tables + window hashing                                  */
+    double ms_sort;             /* the window sort                                                              */
+    double ms_group;            /* unique (k-mer, leaf), CSR offsets, bucket order                              */
+    double ms_d2h;              /* copies of the result to the host                                             */
+    double ms_expand;           /* host: leaves -> explicit node sets (0 with CLS_BUILD_LEAVES_ONLY)            */
+    uint32_t sort_passes;       /* radix passes over the windows                                                */
+    uint32_t full_key;          /* 1: the sort also keyed on the bucket (two k-mers shared a 64-bit hash)      */
+} cls_kmers_info;
+
+/* Build on `device` (-1: the current one).  Bad sizes, flags or a device out of range: CLS_E_INVALID_ARG; a leaf_id
+ * that is not a childless LEAF of the tree: CLS_E_BAD_DB; a build whose device memory exceeds what hipMemGetInfo
+ * reports free: CLS_E_NOMEM.  The views of `b` are borrowed for the call only.  Frees every device allocation it
+ * made, whatever the outcome. */
+int cls_kmers_build(const cls_build_desc* b, int device, cls_kmers** out);
+/* Borrowed view for cls_db_create(): the arrays of `km`, the tree of `b`; node_set_kind follows CLS_BUILD_LEAVES_ONLY
+ * of the build.  Valid while both live. */
+int cls_kmers_desc(const cls_kmers* km, const cls_build_desc* b, cls_db_desc* d);
+int cls_kmers_info_get(const cls_kmers* km, cls_kmers_info* info);
+void cls_kmers_free(cls_kmers* km);
+
 /* ---- FASTA input stage (file_or_stdin.rs:76-116, sequence.rs:47-56) ------ */
 typedef struct cls_fasta {
     uint32_t n;               /* records                                        */
