@@ -187,6 +187,18 @@ class Fasta(C.Structure):
     ]
 
 
+
+class FastqOpts(C.Structure):
+    """cls_fastq_opts: quality cutoffs of the FASTQ stage (0: that end is not trimmed)."""
+    _fields_ = [
+        ("trim_5p", C.c_uint32),
+        ("trim_3p", C.c_uint32),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
+QUERY_FASTA, QUERY_FASTQ = 0, 1  # cls_place_sequences_ex (include/cls_host.h)
+
 class ServiceStats(C.Structure):
     _fields_ = [
         ("jobs_submitted", C.c_uint64),

@@ -864,12 +864,14 @@ extern "C" int cls_place_batch_group(cls_db_group* g, const char* bases, const u
     }
 }
 
-// FASTA text -> records, all on the device: H2D of the file bytes, cls_fasta_scan_device(), placement straight
-// from the scanned bases, D2H of the 24-byte records and of the headers (the output stage needs those on the
-// host).  `fa->bases` / `fa->base_off` come back NULL: the bases never leave the device.
-extern "C" int cls_place_fasta_text(cls_db* db, const char* text, size_t len, const cls_params* params, cls_fasta* fa,
-                                    cls_placement** records) {
-    if (!db || !fa || !records || (!text && len)) return fail(CLS_E_INVALID_ARG, "cls_place_fasta_text: null argument");
+// Query text -> records, all on the device: H2D of the file bytes, `scan` (the device FASTA or FASTQ stage),
+// placement straight from the scanned bases, D2H of the 24-byte records and of the headers (the output stage needs
+// those on the host).  `fa->bases` / `fa->base_off` come back NULL: the bases never leave the device.  `who` names the
+// entry in messages.
+using ScanText = int (*)(const void* d_text, uint64_t len, const void* opts, cls_fasta_dev* out, hipStream_t stream);
+static int place_text(const char* who, cls_db* db, const char* text, size_t len, const cls_params* params, ScanText scan,
+                      const void* scan_opts, cls_fasta* fa, cls_placement** records) {
+    if (!db || !fa || !records || (!text && len)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": null argument");
     memset(fa, 0, sizeof *fa);
     *records = nullptr;
     int prev = 0;
@@ -898,7 +900,7 @@ extern "C" int cls_place_fasta_text(cls_db* db, const char* text, size_t len, co
         CLS_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         CLS_TRY(hipMalloc(&d_text, len ? len : 16));
         if (len) CLS_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, stream));
-        int rc = cls_fasta_scan_device(d_text, len, &dv, stream);
+        int rc = scan(d_text, len, scan_opts, &dv, stream);
         if (rc != CLS_OK) { cleanup(); return rc; }
         (void)hipFree(d_text);
         d_text = nullptr;
@@ -909,7 +911,7 @@ extern "C" int cls_place_fasta_text(cls_db* db, const char* text, size_t len, co
         fa->header_off = (uint64_t*)malloc(((size_t)n + 1) * 8);
         recs = (cls_placement*)malloc(((size_t)n + 1) * sizeof(cls_placement));
         std::vector<uint64_t> boff((size_t)n + 1);
-        if (!fa->headers || !fa->header_off || !recs) { cleanup(); return fail(CLS_E_NOMEM, "cls_place_fasta_text: out of host memory"); }
+        if (!fa->headers || !fa->header_off || !recs) { cleanup(); return fail(CLS_E_NOMEM, std::string(who) + ": out of host memory"); }
         if (dv.n_header_bytes) CLS_TRY(hipMemcpyAsync(fa->headers, dv.d_headers, dv.n_header_bytes, hipMemcpyDeviceToHost, stream));
         CLS_TRY(hipMemcpyAsync(fa->header_off, dv.d_header_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
         CLS_TRY(hipMemcpyAsync(boff.data(), dv.d_base_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
@@ -937,10 +939,27 @@ extern "C" int cls_place_fasta_text(cls_db* db, const char* text, size_t len, co
         return CLS_OK;
     } catch (const std::bad_alloc&) {
         cleanup();
-        return fail(CLS_E_NOMEM, "cls_place_fasta_text: out of host memory");
+        return fail(CLS_E_NOMEM, std::string(who) + ": out of host memory");
     } catch (...) {
         cleanup();
-        return fail(CLS_E_INTERNAL, "cls_place_fasta_text: unknown exception");
+        return fail(CLS_E_INTERNAL, std::string(who) + ": unknown exception");
     }
 #undef CLS_TRY
+}
+
+extern "C" int cls_place_fasta_text(cls_db* db, const char* text, size_t len, const cls_params* params, cls_fasta* fa,
+                                    cls_placement** records) {
+    return place_text("cls_place_fasta_text", db, text, len, params,
+                      [](const void* d, uint64_t n, const void*, cls_fasta_dev* out, hipStream_t st) { return cls_fasta_scan_device(d, n, out, st); },
+                      nullptr, fa, records);
+}
+
+// The FASTQ twin: the device FASTQ stage (parse + quality trimming) in front of the same placement.
+extern "C" int cls_place_fastq_text(cls_db* db, const char* text, size_t len, const cls_params* params, const cls_fastq_opts* opts,
+                                    cls_fasta* fa, cls_placement** records) {
+    return place_text("cls_place_fastq_text", db, text, len, params,
+                      [](const void* d, uint64_t n, const void* o, cls_fasta_dev* out, hipStream_t st) {
+                          return cls_fastq_scan_device(d, n, (const cls_fastq_opts*)o, out, st);
+                      },
+                      opts, fa, records);
 }

@@ -143,3 +143,155 @@ extern "C" int cls_fasta_split(const char* text, size_t len, uint32_t max_pieces
     *n_pieces = np;
     return CLS_OK;
 }
+
+// ---- FASTQ stage (include/cls_place.h states the rules) -------------------------------------------------------
+namespace {
+
+struct FqLine {
+    size_t s, e;      // content [s, e): the terminator, and a '\r' before a '\n', stripped
+    size_t next;      // start of the next line
+};
+
+// the line starting at `pos` (< len)
+FqLine fq_line(const char* text, size_t len, size_t pos) {
+    const char* nl = (const char*)memchr(text + pos, '\n', len - pos);
+    FqLine l{pos, nl ? (size_t)(nl - text) : len, nl ? (size_t)(nl - text) + 1 : len};
+    if (nl && l.e > l.s && text[l.e - 1] == '\r') --l.e;
+    return l;
+}
+
+enum FqStatus { FQ_OK, FQ_END, FQ_BAD };
+
+// The record whose line 1 starts at `pos`: FQ_OK (lines in `l`, `*next` = the start of the next record), FQ_END
+// (nothing but empty lines from `pos` on), FQ_BAD (malformed or incomplete).
+FqStatus fq_record(const char* text, size_t len, size_t pos, FqLine l[4], size_t* next) {
+    if (pos >= len) return FQ_END;
+    l[0] = fq_line(text, len, pos);
+    if (l[0].s == l[0].e) {  // an empty line where a record starts: the end, if nothing but empty lines follow
+        for (size_t p = l[0].next; p < len;) {
+            const FqLine x = fq_line(text, len, p);
+            if (x.s != x.e) return FQ_BAD;
+            p = x.next;
+        }
+        return FQ_END;
+    }
+    for (int k = 1; k < 4; ++k) {
+        if (l[k - 1].next >= len) return FQ_BAD;  // incomplete
+        l[k] = fq_line(text, len, l[k - 1].next);
+    }
+    *next = l[3].next;
+    const size_t L = l[1].e - l[1].s;
+    if (text[l[0].s] != '@' || l[0].e - l[0].s < 2 || text[l[2].s] != '+' || l[3].e - l[3].s != L) return FQ_BAD;
+    if (!valid_utf8((const unsigned char*)text + l[0].s + 1, l[0].e - l[0].s - 1)) return FQ_BAD;
+    for (size_t i = 0; i < L; ++i) {
+        const unsigned char c = (unsigned char)text[l[1].s + i], q = (unsigned char)text[l[3].s + i];
+        if (c >= 0x80 || q < '!' || q > '~') return FQ_BAD;
+    }
+    return FQ_OK;
+}
+
+// the kept window [*start, *stop) of a read of quality `q` (Phred+33 bytes), length L
+void fq_trim(const unsigned char* q, size_t L, uint32_t c5, uint32_t c3, size_t* start, size_t* stop) {
+    const int64_t a = c5 > 94 ? 94 : c5, b = c3 > 94 ? 94 : c3;  // (exact: from 94 on, every step raises the sum)
+    size_t st = 0, sp = L;
+    if (a) {
+        int64_t s = 0, best = 0;
+        for (size_t i = 0; i < L; ++i) {
+            s += a - (q[i] - 33);
+            if (s < 0) break;
+            if (s > best) { best = s; st = i + 1; }
+        }
+    }
+    if (b) {
+        int64_t s = 0, best = 0;
+        for (size_t i = L; i-- > 0;) {
+            s += b - (q[i] - 33);
+            if (s < 0) break;
+            if (s > best) { best = s; sp = i; }
+        }
+    }
+    if (st >= sp) st = sp = 0;
+    *start = st;
+    *stop = sp;
+}
+
+}  // namespace
+
+extern "C" int cls_fastq_parse(const char* text, size_t len, const cls_fastq_opts* opts, cls_fasta* out) {
+    if (!out || (!text && len)) return CLS_E_INVALID_ARG;
+    memset(out, 0, sizeof *out);
+    cls_fastq_opts o{};
+    if (opts) {
+        o = *opts;
+        for (uint32_t r : o.reserved) if (r) return CLS_E_INVALID_ARG;
+    }
+    try {
+        std::string headers, bases;
+        std::vector<uint64_t> hoff{0}, boff{0};
+        bool truncated = false;
+        size_t pos = 0;
+        for (;;) {
+            FqLine l[4];
+            size_t next = 0;
+            const FqStatus st = fq_record(text, len, pos, l, &next);
+            if (st != FQ_OK) { truncated = st == FQ_BAD; break; }
+            if (hoff.size() > 0xFFFFFFFFull) return CLS_E_INVALID_ARG;
+            headers.append(text + l[0].s + 1, l[0].e - l[0].s - 1);
+            hoff.push_back(headers.size());
+            size_t a = 0, b = 0;
+            fq_trim((const unsigned char*)text + l[3].s, l[1].e - l[1].s, o.trim_5p, o.trim_3p, &a, &b);
+            for (size_t i = l[1].s + a; i < l[1].s + b; ++i) {  // sequence.rs:47-56
+                char c = text[i];
+                if (c >= 'a' && c <= 'z') c = (char)(c - 32);
+                if (c == 'A' || c == 'C' || c == 'G' || c == 'T') bases.push_back(c);
+            }
+            boff.push_back(bases.size());
+            pos = next;
+        }
+        out->n = (uint32_t)(hoff.size() - 1);
+        out->truncated = truncated ? 1 : 0;
+        out->headers = (char*)malloc(headers.size() + 1);
+        out->bases = (char*)malloc(bases.size() + 1);
+        out->header_off = (uint64_t*)malloc(hoff.size() * 8);
+        out->base_off = (uint64_t*)malloc(boff.size() * 8);
+        if (!out->headers || !out->bases || !out->header_off || !out->base_off) { cls_fasta_free(out); return CLS_E_NOMEM; }
+        memcpy(out->headers, headers.data(), headers.size());
+        memcpy(out->bases, bases.data(), bases.size());
+        memcpy(out->header_off, hoff.data(), hoff.size() * 8);
+        memcpy(out->base_off, boff.data(), boff.size() * 8);
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        cls_fasta_free(out);
+        return CLS_E_NOMEM;
+    } catch (...) {
+        cls_fasta_free(out);
+        return CLS_E_INTERNAL;
+    }
+}
+
+// Record by record (4 lines at a time, whatever they hold): a cut may follow any well-formed record.
+extern "C" int cls_fastq_split(const char* text, size_t len, uint32_t max_pieces, uint64_t* cuts, uint32_t* n_pieces) {
+    if (!cuts || !n_pieces || max_pieces == 0 || (!text && len)) return CLS_E_INVALID_ARG;
+    uint32_t np = 0;
+    cuts[0] = 0;
+    uint32_t next = 1;  // the next interior target: next * len / max_pieces
+    auto target = [&](uint32_t i) { return (uint64_t)((unsigned __int128)i * len / max_pieces); };
+    size_t pos = 0;
+    while (pos < len && next < max_pieces) {
+        FqLine l[4];
+        size_t end = 0;
+        const FqStatus st = fq_record(text, len, pos, l, &end);
+        if (st == FQ_END) break;
+        if (st == FQ_BAD) {  // skip the record's four lines (or what is left of them): no cut after it
+            end = pos;
+            for (int k = 0; k < 4 && end < len; ++k) end = fq_line(text, len, end).next;
+        } else if (end < len && end >= target(next)) {
+            cuts[++np] = end;
+            while (next < max_pieces && target(next) <= end) ++next;
+        }
+        pos = end;
+    }
+    cuts[++np] = len;
+    *n_pieces = np;
+    return CLS_OK;
+}

@@ -26,6 +26,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <climits>
 #include <string>
 
 #include "cls_place.h"
@@ -365,6 +367,352 @@ extern "C" int cls_fasta_parse_gpu(const char* text, size_t len, int device, cls
     out->header_off = (uint64_t*)malloc(((size_t)dv.n + 1) * 8);
     out->base_off = (uint64_t*)malloc(((size_t)dv.n + 1) * 8);
     if (!out->headers || !out->bases || !out->header_off || !out->base_off) { cleanup(); cls_fasta_free(out); return fa_fail(CLS_E_NOMEM, "cls_fasta_parse_gpu: out of host memory"); }
+    if (dv.n_header_bytes) FA_HIP(hipMemcpy(out->headers, dv.d_headers, dv.n_header_bytes, hipMemcpyDeviceToHost));
+    if (dv.n_bases) FA_HIP(hipMemcpy(out->bases, dv.d_bases, dv.n_bases, hipMemcpyDeviceToHost));
+    FA_HIP(hipMemcpy(out->header_off, dv.d_header_off, ((size_t)dv.n + 1) * 8, hipMemcpyDeviceToHost));
+    FA_HIP(hipMemcpy(out->base_off, dv.d_base_off, ((size_t)dv.n + 1) * 8, hipMemcpyDeviceToHost));
+    cleanup();
+    return CLS_OK;
+}
+
+// ---- FASTQ stage on the device (include/cls_place.h states the rules) -----------------------------------------
+// Record r is lines 4r .. 4r+3 by line index, so the structure needs only the line starts, never the lines' content
+// (a quality line starting with '@' or '+' is no trap).  Passes:
+//   1. per 4096-byte chunk: newlines, last byte that is not part of a line terminator
+//   2. exclusive sum of the newline counts                          [host reads the line count: sync 1]
+//   3. line-start offsets (64-bit) from the newlines' in-chunk ranks
+//   4. one wave per record: validate the four lines, trim (wave64 prefix sums over 64-byte pieces of the quality
+//      line, from the front for the 5' end, from the back for the 3' end, stopping at the first negative running sum),
+//      count the kept bases; the first record that is not well-formed (atomicMin) ends the parse
+//   5. exclusive sums of kept bases and header bytes = the record offset tables
+//   6. where the parse ends, and whether that is a clean end (blank lines only from there on)  [sync 2: sizes]
+//   7. one wave per emitted record: scatter its header bytes and its kept bases (in-wave compaction by ballot)
+namespace {
+
+constexpr int FQ_THREADS = 256, FQ_WAVES = FQ_THREADS / 64;
+enum : uint8_t { FQ_OK = 0, FQ_BAD = 1, FQ_BLANK = 2 };  // record kinds (FQ_BLANK: line 1 is empty)
+
+// the chunk's bytes of thread `tid` (+ one look-ahead byte; '\n' beyond the text)
+__device__ __forceinline__ void fq_load16(const uint8_t* __restrict__ t, uint64_t len, uint64_t base, bool aligned, uint8_t b[FA_PER_THREAD + 1]) {
+    if (aligned && base + FA_PER_THREAD <= len) {
+        const uint4 v = *reinterpret_cast<const uint4*>(t + base);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        for (int k = 0; k < FA_PER_THREAD; ++k) b[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+    } else {
+        for (int k = 0; k < FA_PER_THREAD; ++k) b[k] = byte_at(t, len, base + k);
+    }
+    b[FA_PER_THREAD] = byte_at(t, len, base + FA_PER_THREAD);
+}
+
+// pass 1: newlines per chunk, and the last byte of the chunk that is not '\n' nor a '\r' before a '\n' (-1: none)
+__global__ __launch_bounds__(FQ_THREADS) void fq_count_lines(const uint8_t* __restrict__ text, uint64_t len, bool aligned,
+                                                             uint64_t* __restrict__ cnt_nl, long long* __restrict__ last_text) {
+    typedef hipcub::BlockReduce<uint32_t, FQ_THREADS> SumR;
+    typedef hipcub::BlockReduce<long long, FQ_THREADS> MaxR;
+    __shared__ union { typename SumR::TempStorage s; typename MaxR::TempStorage m; } tmp;
+    const uint64_t base = (uint64_t)blockIdx.x * FA_CHUNK + (uint64_t)threadIdx.x * FA_PER_THREAD;
+    uint8_t b[FA_PER_THREAD + 1];
+    fq_load16(text, len, base, aligned, b);
+    uint32_t n = 0;
+    long long lt = -1;
+    for (int k = 0; k < FA_PER_THREAD; ++k) {
+        const uint64_t i = base + k;
+        if (i >= len) break;
+        if (b[k] == '\n') ++n;
+        else if (!(b[k] == '\r' && i + 1 < len && b[k + 1] == '\n')) lt = (long long)i;
+    }
+    const uint32_t tot = SumR(tmp.s).Sum(n);
+    __syncthreads();
+    const long long mx = MaxR(tmp.m).Reduce(lt, MaxOp());
+    if (threadIdx.x == 0) { cnt_nl[blockIdx.x] = tot; last_text[blockIdx.x] = mx; }
+}
+
+// pass 3: ls[k + 1] = the position after newline k; ls[0] = 0, ls[n_nl + 1] = len + 1 (the end of a last line
+// without a newline, one past the text like a newline's position + 1)
+__global__ __launch_bounds__(FQ_THREADS) void fq_line_starts(const uint8_t* __restrict__ text, uint64_t len, bool aligned,
+                                                             const uint64_t* __restrict__ nl_before, uint64_t n_nl, uint64_t* __restrict__ ls) {
+    typedef hipcub::BlockScan<uint32_t, FQ_THREADS> Scan;
+    __shared__ typename Scan::TempStorage tmp;
+    const uint64_t base = (uint64_t)blockIdx.x * FA_CHUNK + (uint64_t)threadIdx.x * FA_PER_THREAD;
+    uint8_t b[FA_PER_THREAD + 1];
+    fq_load16(text, len, base, aligned, b);
+    uint32_t n = 0;
+    for (int k = 0; k < FA_PER_THREAD; ++k) n += base + k < len && b[k] == '\n';
+    uint32_t rank = 0;
+    Scan(tmp).ExclusiveSum(n, rank);
+    uint64_t o = nl_before[blockIdx.x] + rank;
+    for (int k = 0; k < FA_PER_THREAD; ++k)
+        if (base + k < len && b[k] == '\n' && o < n_nl) ls[++o] = base + k + 1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { ls[0] = 0; ls[n_nl + 1] = len + 1; }
+}
+
+// content [s, e) of line k (k < the line count): "\n" or "\r\n" stripped
+__device__ __forceinline__ void fq_bounds(const uint8_t* __restrict__ t, uint64_t len, const uint64_t* __restrict__ ls, uint64_t k, uint64_t& s, uint64_t& e) {
+    s = ls[k];
+    const uint64_t nx = ls[k + 1];
+    e = nx - 1;
+    if (nx - 1 < len && e > s && t[e - 1] == '\r') --e;
+}
+
+__device__ __forceinline__ int wave_incl_sum(int v, int lane) {
+    for (int o = 1; o < 64; o <<= 1) {
+        const int x = __shfl_up(v, o, 64);
+        if (lane >= o) v += x;
+    }
+    return v;
+}
+
+__device__ __forceinline__ int wave_max(int v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+__device__ __forceinline__ bool is_acgt(uint8_t c) {
+    const uint8_t u = (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c;
+    return u == 'A' || u == 'C' || u == 'G' || u == 'T';
+}
+
+// One end of the trimming rule on the quality bytes q[0, L), by the whole wave: the running sum s of c - q[i] over
+// pieces of 64 positions (from the front, or from the back when `from_end`), lanes in visiting order, stops at the
+// first negative s; the result is the position after (front) / at (back) the first visit that reached the maximum
+// s > 0, else `dflt`.
+__device__ uint64_t wave_trim(const uint8_t* __restrict__ q, uint64_t L, int c, bool from_end, int lane, uint64_t dflt) {
+    long long carry = 0, best = 0;
+    uint64_t res = dflt;
+    for (uint64_t base = 0; base < L; base += 64) {
+        const uint64_t j = base + (uint64_t)lane;
+        const bool valid = j < L;
+        const int d = valid ? c - ((int)q[from_end ? L - 1 - j : j] - 33) : 0;
+        const int p = wave_incl_sum(d, lane);
+        const unsigned long long neg = __ballot(valid && carry + p < 0);
+        const int lim = neg ? __ffsll((unsigned long long)neg) - 1 : 64;
+        const bool cand = valid && lane < lim;
+        const int pm = wave_max(cand ? p : INT_MIN);
+        if (pm != INT_MIN && carry + pm > best) {
+            best = carry + pm;
+            const uint64_t jf = base + (uint64_t)(__ffsll((unsigned long long)__ballot(cand && p == pm)) - 1);
+            res = from_end ? L - 1 - jf : jf + 1;
+        }
+        if (neg) break;
+        carry += __shfl(p, 63, 64);
+    }
+    return res;
+}
+
+// pass 4: one wave per record candidate r < n_cand (line 4r exists)
+__global__ __launch_bounds__(FQ_THREADS) void fq_records(const uint8_t* __restrict__ text, uint64_t len, const uint64_t* __restrict__ ls,
+                                                         uint64_t n_lines, uint64_t n_cand, int c5, int c3, uint64_t* __restrict__ nb,
+                                                         uint64_t* __restrict__ nh, uint64_t* __restrict__ win, uint8_t* __restrict__ kind,
+                                                         unsigned long long* __restrict__ first_stop) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t r = (uint64_t)blockIdx.x * FQ_WAVES + (threadIdx.x >> 6);
+    if (r >= n_cand) return;
+    uint64_t s[4], e[4];
+    fq_bounds(text, len, ls, 4 * r, s[0], e[0]);
+    uint8_t k = FQ_OK;
+    if (s[0] == e[0]) k = FQ_BLANK;
+    else if (4 * r + 3 >= n_lines) k = FQ_BAD;  // incomplete
+    uint64_t L = 0, lo = 0, hi = 0, cnt = 0;
+    if (k == FQ_OK) {
+        for (int x = 1; x < 4; ++x) fq_bounds(text, len, ls, 4 * r + x, s[x], e[x]);
+        L = e[1] - s[1];
+        bool ok = text[s[0]] == '@' && e[0] - s[0] >= 2 && text[s[2]] == '+' && e[3] - s[3] == L;
+        bool bad = false;
+        if (ok)
+            for (uint64_t i = s[0] + 1 + lane; i < e[0]; i += 64) bad |= text[i] >= 0x80 && !utf8_ok_at(text, len, i);
+        if (ok)
+            for (uint64_t j = lane; j < L; j += 64) {
+                const uint8_t c = text[s[1] + j], q = text[s[3] + j];
+                bad |= c >= 0x80 || q < '!' || q > '~';
+            }
+        ok = ok && !__any(bad);
+        if (!ok) k = FQ_BAD;
+    }
+    if (k == FQ_OK) {
+        const uint8_t* q = text + s[3];
+        const uint64_t a = c5 ? wave_trim(q, L, c5, false, lane, 0) : 0;
+        const uint64_t b = c3 ? wave_trim(q, L, c3, true, lane, L) : L;
+        if (a < b) { lo = s[1] + a; hi = s[1] + b; }
+        for (uint64_t p = lo; p < hi; p += 64) {
+            const uint64_t i = p + (uint64_t)lane;
+            cnt += __popcll(__ballot(i < hi && is_acgt(text[i])));
+        }
+    }
+    if (lane == 0) {
+        kind[r] = k;
+        nb[r] = cnt;
+        nh[r] = k == FQ_OK ? e[0] - s[0] - 1 : 0;
+        win[2 * r] = lo;
+        win[2 * r + 1] = hi;
+        if (k != FQ_OK) atomicMin(first_stop, (unsigned long long)r);
+    }
+}
+
+// pass 6: res = {records emitted, truncated, kept bases, header bytes}
+__global__ __launch_bounds__(FQ_THREADS) void fq_finish(const uint64_t* __restrict__ ls, uint64_t n_cand, const uint8_t* __restrict__ kind,
+                                                        const long long* __restrict__ last_text, uint64_t n_chunks,
+                                                        const uint64_t* __restrict__ base_off, const uint64_t* __restrict__ hdr_off,
+                                                        const unsigned long long* __restrict__ first_stop, unsigned long long* __restrict__ res) {
+    const uint64_t rs = *first_stop;
+    const uint64_t n = rs < n_cand ? rs : n_cand;
+    bool trunc = false;
+    if (rs < n_cand) {
+        if (kind[rs] == FQ_BAD) trunc = true;
+        else {  // an empty line where record rs starts: a clean end iff no line after it holds anything
+            const uint64_t P = ls[4 * rs];
+            for (uint64_t c0 = P / FA_CHUNK; c0 < n_chunks; c0 += FQ_THREADS) {
+                const uint64_t c = c0 + threadIdx.x;
+                if (__syncthreads_or(c < n_chunks && last_text[c] >= (long long)P))  { trunc = true; break; }
+            }
+        }
+    }
+    if (threadIdx.x == 0) { res[0] = n; res[1] = trunc ? 1 : 0; res[2] = base_off[n]; res[3] = hdr_off[n]; }
+}
+
+// pass 7: one wave per emitted record
+__global__ __launch_bounds__(FQ_THREADS) void fq_scatter(const uint8_t* __restrict__ text, const uint64_t* __restrict__ ls, uint64_t n,
+                                                         const uint64_t* __restrict__ win, const uint64_t* __restrict__ base_off,
+                                                         const uint64_t* __restrict__ hdr_off, uint8_t* __restrict__ bases,
+                                                         uint8_t* __restrict__ headers) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t r = (uint64_t)blockIdx.x * FQ_WAVES + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const uint64_t hs = ls[4 * r] + 1, ho = hdr_off[r], hn = hdr_off[r + 1] - ho;
+    for (uint64_t j = lane; j < hn; j += 64) headers[ho + j] = text[hs + j];
+    const uint64_t lo = win[2 * r], hi = win[2 * r + 1], end = base_off[r + 1];
+    uint64_t o = base_off[r];
+    const unsigned long long below = (1ull << lane) - 1;
+    for (uint64_t p = lo; p < hi; p += 64) {
+        const uint64_t i = p + (uint64_t)lane;
+        const uint8_t c = i < hi ? text[i] : (uint8_t)0;
+        const bool keep = i < hi && is_acgt(c);
+        const unsigned long long m = __ballot(keep);
+        const uint64_t dst = o + (uint64_t)__popcll(m & below);
+        if (keep && dst < end) bases[dst] = (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c;
+        o += (uint64_t)__popcll(m);
+    }
+}
+
+}  // namespace
+
+extern "C" int cls_fastq_scan_device(const void* d_text, uint64_t len, const cls_fastq_opts* opts, cls_fasta_dev* out, void* hip_stream) {
+    if (!out || (!d_text && len)) return fa_fail(CLS_E_INVALID_ARG, "cls_fastq_scan_device: null argument");
+    memset(out, 0, sizeof *out);
+    cls_fastq_opts o{};
+    if (opts) {
+        o = *opts;
+        for (uint32_t x : o.reserved) if (x) return fa_fail(CLS_E_INVALID_ARG, "cls_fastq_scan_device: reserved options must be 0");
+    }
+    const int c5 = (int)std::min<uint32_t>(o.trim_5p, 94), c3 = (int)std::min<uint32_t>(o.trim_3p, 94);  // (exact, cls_place.h)
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const uint8_t* text = (const uint8_t*)d_text;
+    const bool aligned = ((uintptr_t)d_text & 15) == 0;
+    const uint64_t n_chunks = (len + FA_CHUNK - 1) / FA_CHUNK;
+    uint64_t *d_cnt = nullptr, *d_ls = nullptr, *d_win = nullptr;
+    long long* d_lt = nullptr;
+    uint8_t* d_kind = nullptr;
+    unsigned long long* d_misc = nullptr;  // [0] first record that is not well-formed, [1..4] fq_finish's result
+    void* d_tmp = nullptr;
+    bool ok = false;
+    auto cleanup = [&]() {
+        for (void* p : {(void*)d_cnt, (void*)d_ls, (void*)d_win, (void*)d_lt, (void*)d_kind, (void*)d_misc, d_tmp}) if (p) (void)hipFree(p);
+        d_cnt = d_ls = d_win = nullptr; d_lt = nullptr; d_kind = nullptr; d_misc = nullptr; d_tmp = nullptr;
+        if (!ok) cls_fasta_dev_free(out);
+    };
+    try {
+        if (n_chunks == 0) {
+            FA_HIP(hipMalloc(&out->d_bases, 16));
+            FA_HIP(hipMalloc(&out->d_headers, 16));
+            FA_HIP(hipMalloc((void**)&out->d_base_off, 16));
+            FA_HIP(hipMalloc((void**)&out->d_header_off, 16));
+            FA_HIP(hipMemsetAsync(out->d_base_off, 0, 16, stream));
+            FA_HIP(hipMemsetAsync(out->d_header_off, 0, 16, stream));
+            FA_HIP(hipStreamSynchronize(stream));
+            ok = true;
+            cleanup();
+            return CLS_OK;
+        }
+        FA_HIP(hipMalloc((void**)&d_misc, 8 * sizeof(unsigned long long)));
+        FA_HIP(hipMemsetAsync(d_misc, 0xFF, 8, stream));
+        FA_HIP(hipMalloc((void**)&d_cnt, (n_chunks + 1) * 8));
+        FA_HIP(hipMalloc((void**)&d_lt, n_chunks * 8));
+        FA_HIP(hipMemsetAsync(d_cnt + n_chunks, 0, 8, stream));
+        hipLaunchKernelGGL(fq_count_lines, dim3((unsigned)n_chunks), dim3(FQ_THREADS), 0, stream, text, len, aligned, d_cnt, d_lt);
+        size_t tmp_bytes = 0;
+        FA_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_cnt, d_cnt, (int)(n_chunks + 1), stream));
+        FA_HIP(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
+        FA_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_cnt, d_cnt, (int)(n_chunks + 1), stream));
+        uint64_t n_nl = 0;
+        uint8_t last = 0;
+        FA_HIP(hipMemcpyAsync(&n_nl, d_cnt + n_chunks, 8, hipMemcpyDeviceToHost, stream));
+        FA_HIP(hipMemcpyAsync(&last, text + len - 1, 1, hipMemcpyDeviceToHost, stream));
+        FA_HIP(hipStreamSynchronize(stream));  // sync 1: the line count
+        const uint64_t n_lines = n_nl + (last != '\n' ? 1 : 0), n_cand = (n_lines + 3) / 4;
+        FA_HIP(hipMalloc((void**)&d_ls, (n_nl + 2) * 8));
+        hipLaunchKernelGGL(fq_line_starts, dim3((unsigned)n_chunks), dim3(FQ_THREADS), 0, stream, text, len, aligned, d_cnt, n_nl, d_ls);
+        FA_HIP(hipMalloc((void**)&out->d_base_off, (n_cand + 1) * 8));
+        FA_HIP(hipMalloc((void**)&out->d_header_off, (n_cand + 1) * 8));
+        FA_HIP(hipMalloc((void**)&d_win, 2 * n_cand * 8));
+        FA_HIP(hipMalloc((void**)&d_kind, n_cand));
+        uint64_t* nb = (uint64_t*)out->d_base_off;
+        uint64_t* nh = (uint64_t*)out->d_header_off;
+        FA_HIP(hipMemsetAsync(nb + n_cand, 0, 8, stream));
+        FA_HIP(hipMemsetAsync(nh + n_cand, 0, 8, stream));
+        hipLaunchKernelGGL(fq_records, dim3((unsigned)((n_cand + FQ_WAVES - 1) / FQ_WAVES)), dim3(FQ_THREADS), 0, stream, text, len, d_ls, n_lines,
+                           n_cand, c5, c3, nb, nh, d_win, d_kind, d_misc);
+        size_t need = 0;
+        FA_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, nb, nb, (int)(n_cand + 1), stream));
+        if (need > tmp_bytes) { (void)hipFree(d_tmp); d_tmp = nullptr; FA_HIP(hipMalloc(&d_tmp, need)); tmp_bytes = need; }
+        FA_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, nb, nb, (int)(n_cand + 1), stream));
+        FA_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, nh, nh, (int)(n_cand + 1), stream));
+        hipLaunchKernelGGL(fq_finish, dim3(1), dim3(FQ_THREADS), 0, stream, d_ls, n_cand, d_kind, d_lt, n_chunks, nb, nh, d_misc, d_misc + 1);
+        unsigned long long res[4] = {0, 0, 0, 0};
+        FA_HIP(hipMemcpyAsync(res, d_misc + 1, sizeof res, hipMemcpyDeviceToHost, stream));
+        FA_HIP(hipStreamSynchronize(stream));  // sync 2: the output sizes
+        if (hipGetLastError() != hipSuccess) { cleanup(); return fa_fail(CLS_E_HIP, "cls_fastq_scan_device: kernel launch failed"); }
+        if (res[0] > 0xFFFFFFFFull) { cleanup(); return fa_fail(CLS_E_INVALID_ARG, "cls_fastq_scan_device: more than 2^32 records"); }
+        out->n = (uint32_t)res[0];
+        out->truncated = (uint32_t)res[1];
+        out->n_bases = res[2];
+        out->n_header_bytes = res[3];
+        FA_HIP(hipMalloc(&out->d_bases, res[2] ? res[2] : 16));
+        FA_HIP(hipMalloc(&out->d_headers, res[3] ? res[3] : 16));
+        if (res[0])
+            hipLaunchKernelGGL(fq_scatter, dim3((unsigned)((res[0] + FQ_WAVES - 1) / FQ_WAVES)), dim3(FQ_THREADS), 0, stream, text, d_ls, res[0], d_win,
+                               nb, nh, (uint8_t*)out->d_bases, (uint8_t*)out->d_headers);
+        if (hipGetLastError() != hipSuccess) { cleanup(); return fa_fail(CLS_E_HIP, "cls_fastq_scan_device: kernel launch failed"); }
+        // (the temporaries are freed below; hipFree waits for the work that still reads them)
+        ok = true;
+        cleanup();
+        return CLS_OK;
+    } catch (...) {
+        cleanup();
+        return fa_fail(CLS_E_INTERNAL, "cls_fastq_scan_device: unknown exception");
+    }
+}
+
+// Host text in, host records out, through the device passes (what the tests compare with cls_fastq_parse).
+extern "C" int cls_fastq_parse_gpu(const char* text, size_t len, const cls_fastq_opts* opts, int device, cls_fasta* out) {
+    if (!out || (!text && len)) return fa_fail(CLS_E_INVALID_ARG, "cls_fastq_parse_gpu: null argument");
+    memset(out, 0, sizeof *out);
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) return fa_fail(CLS_E_NO_DEVICE, "cls_fastq_parse_gpu: no HIP device is visible");
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return fa_fail(CLS_E_INVALID_ARG, "cls_fastq_parse_gpu: bad device ordinal");
+    void* d_text = nullptr;
+    cls_fasta_dev dv;
+    memset(&dv, 0, sizeof dv);
+    auto cleanup = [&]() { if (d_text) (void)hipFree(d_text); cls_fasta_dev_free(&dv); };
+    FA_HIP(hipMalloc(&d_text, len ? len : 16));
+    if (len) FA_HIP(hipMemcpy(d_text, text, len, hipMemcpyHostToDevice));
+    int rc = cls_fastq_scan_device(d_text, len, opts, &dv, nullptr);
+    if (rc != CLS_OK) { cleanup(); return rc; }
+    out->n = dv.n;
+    out->truncated = dv.truncated;
+    out->headers = (char*)malloc(dv.n_header_bytes + 1);
+    out->bases = (char*)malloc(dv.n_bases + 1);
+    out->header_off = (uint64_t*)malloc(((size_t)dv.n + 1) * 8);
+    out->base_off = (uint64_t*)malloc(((size_t)dv.n + 1) * 8);
+    if (!out->headers || !out->bases || !out->header_off || !out->base_off) { cleanup(); cls_fasta_free(out); return fa_fail(CLS_E_NOMEM, "cls_fastq_parse_gpu: out of host memory"); }
     if (dv.n_header_bytes) FA_HIP(hipMemcpy(out->headers, dv.d_headers, dv.n_header_bytes, hipMemcpyDeviceToHost));
     if (dv.n_bases) FA_HIP(hipMemcpy(out->bases, dv.d_bases, dv.n_bases, hipMemcpyDeviceToHost));
     FA_HIP(hipMemcpy(out->header_off, dv.d_header_off, ((size_t)dv.n + 1) * 8, hipMemcpyDeviceToHost));

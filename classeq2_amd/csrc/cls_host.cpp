@@ -762,26 +762,59 @@ static int place_sequences_with(const char* who, const cls_tree* t, const char* 
     }
 }
 
-extern "C" int cls_place_sequences(cls_db* db, const cls_tree* t, const char* query_path, const char* out_file,
-                                   const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds) {
+// The query format of the _ex entries: the FASTA stage, or the FASTQ stage with its options.
+struct QueryFormat {
+    int kind = CLS_QUERY_FASTA;
+    cls_fastq_opts fastq{};
+};
+
+static int check_query_format(const char* who, int query_format, const cls_fastq_opts* fastq, QueryFormat* q) {
+    if (query_format != CLS_QUERY_FASTA && query_format != CLS_QUERY_FASTQ) return fail(CLS_E_INVALID_ARG, std::string(who) + ": unknown query format");
+    q->kind = query_format;
+    if (fastq) q->fastq = *fastq;
+    if (query_format == CLS_QUERY_FASTA && (q->fastq.trim_5p || q->fastq.trim_3p))
+        return fail(CLS_E_INVALID_ARG, std::string(who) + ": quality trimming needs FASTQ queries");
+    for (uint32_t r : q->fastq.reserved)
+        if (r) return fail(CLS_E_INVALID_ARG, std::string(who) + ": reserved FASTQ options must be 0");
+    return CLS_OK;
+}
+
+static int place_text_one(cls_db* db, const char* text, size_t len, const cls_params* params, const QueryFormat& q, cls_fasta* fa,
+                          cls_placement** recs) {
+    return q.kind == CLS_QUERY_FASTQ ? cls_place_fastq_text(db, text, len, params, &q.fastq, fa, recs)
+                                     : cls_place_fasta_text(db, text, len, params, fa, recs);
+}
+
+extern "C" int cls_place_sequences_ex(cls_db* db, const cls_tree* t, const char* query_path, const char* out_file, const cls_params* params,
+                                      int overwrite, int format, int query_format, const cls_fastq_opts* fastq, uint32_t* n_placed,
+                                      double* seconds) {
     if (!db || !t || !query_path || !out_file) return fail(CLS_E_INVALID_ARG, "cls_place_sequences: null argument");
+    QueryFormat q;
+    if (int rc = check_query_format("cls_place_sequences", query_format, fastq, &q)) return rc;
     return place_sequences_with("cls_place_sequences", t, query_path, out_file, overwrite, format, n_placed, seconds,
                                 [&](const std::string& text, cls_fasta* fa, cls_placement** recs) {
-                                    int rc = cls_place_fasta_text(db, text.data(), text.size(), params, fa, recs);
+                                    int rc = place_text_one(db, text.data(), text.size(), params, q, fa, recs);
                                     if (rc != CLS_OK) { std::string m = cls_last_error(); return fail(rc, m); }
                                     return CLS_OK;
                                 });
 }
 
+extern "C" int cls_place_sequences(cls_db* db, const cls_tree* t, const char* query_path, const char* out_file,
+                                   const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds) {
+    return cls_place_sequences_ex(db, t, query_path, out_file, params, overwrite, format, CLS_QUERY_FASTA, nullptr, n_placed, seconds);
+}
+
 // One piece per replica (cls_fasta_split), placed on the replicas' own threads, joined in input order.
-static int place_text_group(cls_db_group* grp, const std::string& text, const cls_params* params, cls_fasta* fa, cls_placement** recs) {
+static int place_text_group(cls_db_group* grp, const std::string& text, const cls_params* params, const QueryFormat& q, cls_fasta* fa,
+                            cls_placement** recs) {
     uint32_t n_rep = 0;
     int rc = cls_db_group_size(grp, &n_rep);
     if (rc != CLS_OK) return fail(rc, cls_last_error());
     std::vector<uint64_t> cuts((size_t)n_rep + 1);
     uint32_t n_pieces = 0;
-    rc = cls_fasta_split(text.data(), text.size(), n_rep, cuts.data(), &n_pieces);
-    if (rc != CLS_OK) return fail(rc, "cls_place_sequences_group: cls_fasta_split failed");
+    const bool fastq = q.kind == CLS_QUERY_FASTQ;
+    rc = (fastq ? cls_fastq_split : cls_fasta_split)(text.data(), text.size(), n_rep, cuts.data(), &n_pieces);
+    if (rc != CLS_OK) return fail(rc, fastq ? "cls_place_sequences_group: cls_fastq_split failed" : "cls_place_sequences_group: cls_fasta_split failed");
     struct Piece {
         cls_fasta fa{};
         cls_placement* recs = nullptr;
@@ -801,7 +834,7 @@ static int place_text_group(cls_db_group* grp, const std::string& text, const cl
         if (p.rc == CLS_OK) p.rc = cls_db_info_get(db, &info);
         if (p.rc == CLS_OK) {
             devices[i] = info.device;
-            p.rc = cls_place_fasta_text(db, text.data() + cuts[i], cuts[i + 1] - cuts[i], params, &p.fa, &p.recs);
+            p.rc = place_text_one(db, text.data() + cuts[i], cuts[i + 1] - cuts[i], params, q, &p.fa, &p.recs);
         }
         if (p.rc != CLS_OK) p.msg = cls_last_error();  // (the message is the worker's own: hand it back)
     };
@@ -846,11 +879,20 @@ static int place_text_group(cls_db_group* grp, const std::string& text, const cl
     return CLS_OK;
 }
 
-extern "C" int cls_place_sequences_group(cls_db_group* grp, const cls_tree* t, const char* query_path, const char* out_file,
-                                         const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds) {
+extern "C" int cls_place_sequences_group_ex(cls_db_group* grp, const cls_tree* t, const char* query_path, const char* out_file,
+                                            const cls_params* params, int overwrite, int format, int query_format,
+                                            const cls_fastq_opts* fastq, uint32_t* n_placed, double* seconds) {
     if (!grp || !t || !query_path || !out_file) return fail(CLS_E_INVALID_ARG, "cls_place_sequences_group: null argument");
+    QueryFormat q;
+    if (int rc = check_query_format("cls_place_sequences_group", query_format, fastq, &q)) return rc;
     return place_sequences_with("cls_place_sequences_group", t, query_path, out_file, overwrite, format, n_placed, seconds,
                                 [&](const std::string& text, cls_fasta* fa, cls_placement** recs) {
-                                    return place_text_group(grp, text, params, fa, recs);
+                                    return place_text_group(grp, text, params, q, fa, recs);
                                 });
+}
+
+extern "C" int cls_place_sequences_group(cls_db_group* grp, const cls_tree* t, const char* query_path, const char* out_file,
+                                         const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds) {
+    return cls_place_sequences_group_ex(grp, t, query_path, out_file, params, overwrite, format, CLS_QUERY_FASTA, nullptr, n_placed,
+                                        seconds);
 }

@@ -1,7 +1,7 @@
 // cls-place: C++ look-alike of the reference's `cls place` sub-command
 // (ports/cli/src/cmds/place_sequences.rs:18-82 flag surface, :84-223 behaviour) on the GPU path.
 //   cls-place [QUERY|-] -d DB -o OUT [-a ANNOTATIONS.yaml] [--out-format yaml|jsonl]
-//             [-i N] [-m COV] [-r] [-f] [--device N[,N...]]
+//             [-i N] [-m COV] [-r] [-f] [--device N[,N...]] [--query-format fasta|fastq] [-q [5P,]3P]
 // The database is read like load_database does (ports/lib/src/functions/load_database.rs:9-53): the `.cls`
 // file of `cls build-db` (zstd-compressed YAML), plain YAML, or the JSON export.
 #include <stdio.h>
@@ -16,7 +16,7 @@
 static void usage() {
     fprintf(stderr,
             "Usage: cls-place [QUERY] --database-file-path <DB> --output-file-path <OUT> [OPTIONS]\n\n"
-            "Arguments:\n  [QUERY]  multi-FASTA file, or \"-\" for STDIN [default: -]\n\n"
+            "Arguments:\n  [QUERY]  multi-FASTA (or, with --query-format fastq, FASTQ) file, or \"-\" for STDIN [default: -]\n\n"
             "Options:\n"
             "  -d, --database-file-path <PATH>     classeq database (.cls, .cls.yaml or .cls.json)\n"
             "  -o, --output-file-path <PATH>       output file (extension replaced by .yaml / .jsonl; errors go to .error)\n"
@@ -27,7 +27,24 @@ static void usage() {
             "  -r, --remove-intersection           one-vs-rest without the shared k-mers\n"
             "  -f, --force-overwrite               overwrite an existing output file\n"
             "      --device <N[,N...]>             GPU ordinal [default: 0]; a comma list places on one replica of the\n"
-            "                                      index per entry (repeats allowed)\n");
+            "                                      index per entry (repeats allowed)\n"
+            "      --query-format <fasta|fastq>    format of QUERY [default: fasta]; fastq = strict four-line FASTQ, Phred+33\n"
+            "  -q, --trim-quality <[5P,]3P>        fastq only: trim low-quality ends (BWA / cutadapt -q rule); one value\n"
+            "                                      trims the 3' end, two values the 5' and the 3' end [default: 0,0 = off]\n");
+}
+
+// cutadapt's -q: "3P" or "5P,3P", each a cutoff in 0 .. 2^31 - 1
+static bool parse_cutoffs(const std::string& v, uint32_t* c5, uint32_t* c3) {
+    const size_t comma = v.find(',');
+    auto one = [](const std::string& x, uint32_t* c) {
+        if (x.empty() || x.size() > 10 || x.find_first_not_of("0123456789") != std::string::npos) return false;
+        const unsigned long long n = strtoull(x.c_str(), nullptr, 10);
+        if (n > 0x7FFFFFFFull) return false;
+        *c = (uint32_t)n;
+        return true;
+    };
+    if (comma == std::string::npos) { *c5 = 0; return one(v, c3); }
+    return one(v.substr(0, comma), c5) && one(v.substr(comma + 1), c3);
 }
 
 int main(int argc, char** argv) {
@@ -36,6 +53,9 @@ int main(int argc, char** argv) {
     memset(&p, 0, sizeof p);
     int overwrite = 0, device = 0;
     std::vector<int> devices;  // --device with a comma: an index group, one replica per entry
+    std::string qfmt = "fasta", trim;
+    cls_fastq_opts fq;
+    memset(&fq, 0, sizeof fq);
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char* name) -> const char* {
@@ -67,11 +87,19 @@ int main(int argc, char** argv) {
                 }
             }
         }
+        else if (a == "--query-format") qfmt = need("--query-format");
+        else if (a == "-q" || a == "--trim-quality") trim = need("--trim-quality");
         else if (!a.empty() && a[0] == '-' && a != "-") { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); usage(); return 2; }
         else query = a;
     }
     if (db_path.empty() || out_path.empty()) { usage(); return 2; }
     if (fmt != "yaml" && fmt != "jsonl") { fprintf(stderr, "error: invalid value '%s' for '--out-format'\n", fmt.c_str()); return 2; }
+    if (qfmt != "fasta" && qfmt != "fastq") { fprintf(stderr, "error: invalid value '%s' for '--query-format'\n", qfmt.c_str()); return 2; }
+    if (!trim.empty()) {
+        if (qfmt != "fastq") { fprintf(stderr, "error: '--trim-quality' needs '--query-format fastq'\n"); return 2; }
+        if (!parse_cutoffs(trim, &fq.trim_5p, &fq.trim_3p)) { fprintf(stderr, "error: invalid value '%s' for '--trim-quality'\n", trim.c_str()); return 2; }
+    }
+    const int query_format = qfmt == "fastq" ? CLS_QUERY_FASTQ : CLS_QUERY_FASTA;
 
     cls_tree* tree = nullptr;
     if (cls_tree_load(db_path.c_str(), &tree) != CLS_OK) { fprintf(stderr, "Error loading database: %s\n", cls_host_last_error()); return 1; }
@@ -92,8 +120,9 @@ int main(int argc, char** argv) {
     uint32_t n = 0;
     double seconds = 0;
     const int format = fmt == "yaml" ? CLS_FORMAT_YAML : CLS_FORMAT_JSONL;
-    int rc = db ? cls_place_sequences(db, tree, query.c_str(), out_path.c_str(), &p, overwrite, format, &n, &seconds)
-                : cls_place_sequences_group(group, tree, query.c_str(), out_path.c_str(), &p, overwrite, format, &n, &seconds);
+    int rc = db ? cls_place_sequences_ex(db, tree, query.c_str(), out_path.c_str(), &p, overwrite, format, query_format, &fq, &n, &seconds)
+                : cls_place_sequences_group_ex(group, tree, query.c_str(), out_path.c_str(), &p, overwrite, format, query_format, &fq, &n,
+                                               &seconds);
     if (rc != CLS_OK) fprintf(stderr, "%s\n", cls_host_last_error());
     else fprintf(stderr, "{\"code\":\"CLIPLACE0002\",\"sequences\":%u,\"totalSeconds\":%.6f,\"averageSeconds\":%.9f}\n", n, seconds, n ? seconds / n : 0.0);
     cls_db_destroy(db);

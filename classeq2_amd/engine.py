@@ -26,12 +26,14 @@ EXPORTS = [
     "cls_db_read_classes", "cls_db_set_max_read_len", "cls_place_batch",
     "cls_db_group_create", "cls_db_group_destroy", "cls_db_group_size", "cls_db_group_replica", "cls_place_batch_group", "cls_fasta_split",
     "cls_place_batch_device", "cls_place_batch_stats", "cls_fasta_parse", "cls_fasta_free", "cls_fasta_scan_device", "cls_fasta_dev_free",
-    "cls_fasta_parse_gpu", "cls_place_fasta_text", "cls_last_error",
+    "cls_fasta_parse_gpu", "cls_place_fasta_text", "cls_fastq_parse", "cls_fastq_split", "cls_fastq_scan_device", "cls_fastq_parse_gpu",
+    "cls_place_fastq_text", "cls_last_error",
     "cls_version", "cls_set_tuning", "cls_tuning_from_env", "cls_kmers_build", "cls_kmers_desc", "cls_kmers_info_get", "cls_kmers_free",
 ]
 HOST_EXPORTS = [
     "cls_tree_load_json", "cls_tree_load", "cls_tree_init_from_file", "cls_tree_from_newick", "cls_tree_serialize", "cls_tree_save", "cls_tree_free", "cls_tree_set_annotations_yaml", "cls_tree_build_kmers_map", "cls_tree_build_kmers_map_device", "cls_tree_desc", "cls_serialize_results",
-    "cls_host_free", "cls_place_sequences", "cls_place_sequences_group", "cls_host_last_error",
+    "cls_host_free", "cls_place_sequences", "cls_place_sequences_group", "cls_place_sequences_ex", "cls_place_sequences_group_ex",
+    "cls_host_last_error",
 ]
 SERVICE_EXPORTS = [
     "cls_service_create", "cls_service_destroy", "cls_service_add_model", "cls_service_submit", "cls_service_wait", "cls_service_pause",
@@ -99,6 +101,15 @@ def lib():
         L.cls_fasta_parse_gpu.restype = i32
         L.cls_place_fasta_text.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params), C.POINTER(_abi.Fasta), C.POINTER(vp)]
         L.cls_place_fasta_text.restype = i32
+        L.cls_fastq_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_abi.FastqOpts), C.POINTER(_abi.Fasta)]
+        L.cls_fastq_parse.restype = i32
+        L.cls_fastq_parse_gpu.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_abi.FastqOpts), i32, C.POINTER(_abi.Fasta)]
+        L.cls_fastq_parse_gpu.restype = i32
+        L.cls_fastq_split.argtypes = [C.c_char_p, C.c_size_t, u32, C.POINTER(C.c_uint64), C.POINTER(u32)]
+        L.cls_fastq_split.restype = i32
+        L.cls_place_fastq_text.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params), C.POINTER(_abi.FastqOpts), C.POINTER(_abi.Fasta),
+                                           C.POINTER(vp)]
+        L.cls_place_fastq_text.restype = i32
         L.cls_fasta_free.argtypes = [C.POINTER(_abi.Fasta)]
         L.cls_fasta_free.restype = None
         L.cls_last_error.restype = C.c_char_p
@@ -149,6 +160,10 @@ def lib():
         L.cls_place_sequences_group.argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.POINTER(_abi.Params), i32, i32,
                                                 C.POINTER(u32), C.POINTER(C.c_double)]
         L.cls_place_sequences_group.restype = i32
+        for name in ("cls_place_sequences_ex", "cls_place_sequences_group_ex"):
+            getattr(L, name).argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.POINTER(_abi.Params), i32, i32, i32, C.POINTER(_abi.FastqOpts),
+                                         C.POINTER(u32), C.POINTER(C.c_double)]
+            getattr(L, name).restype = i32
         L.cls_host_last_error.restype = C.c_char_p
         # resident batching service (include/cls_service.h)
         L.cls_service_create.argtypes = [C.POINTER(vp)]
@@ -227,6 +242,41 @@ def fasta_parse(text: bytes, device: Optional[int] = None):
         return headers, bases, boff, bool(f.truncated)
     finally:
         lib().cls_fasta_free(C.byref(f))
+
+
+def _fastq_opts(trim_5p: int = 0, trim_3p: int = 0) -> _abi.FastqOpts:
+    o = _abi.FastqOpts()
+    o.trim_5p, o.trim_3p = int(trim_5p), int(trim_3p)
+    return o
+
+
+def fastq_parse(text: bytes, device: Optional[int] = None, trim_5p: int = 0, trim_3p: int = 0):
+    """Strict four-line FASTQ, quality-trimmed (include/cls_place.h) -> the tuple of fasta_parse.
+    `device`: run the stage's data-parallel passes on that GPU (cls_fastq_parse_gpu) instead of the host parser."""
+    f = _abi.Fasta()
+    o = _fastq_opts(trim_5p, trim_3p)
+    if device is None:
+        _check(lib().cls_fastq_parse(text, len(text), C.byref(o), C.byref(f)))
+    else:
+        _check(lib().cls_fastq_parse_gpu(text, len(text), C.byref(o), device, C.byref(f)))
+    try:
+        n = f.n
+        hoff = np.ctypeslib.as_array(f.header_off, shape=(n + 1,)).copy()
+        boff = np.ctypeslib.as_array(f.base_off, shape=(n + 1,)).copy()
+        hraw = C.string_at(f.headers, int(hoff[-1]))
+        bases = np.frombuffer(C.string_at(f.bases, int(boff[-1])), dtype=np.uint8).copy()
+        headers = [hraw[int(hoff[i]) : int(hoff[i + 1])] for i in range(n)]
+        return headers, bases, boff, bool(f.truncated)
+    finally:
+        lib().cls_fasta_free(C.byref(f))
+
+
+def fastq_split(text: bytes, max_pieces: int) -> list:
+    """Cut points for parsing FASTQ `text` in up to `max_pieces` pieces (cls_fastq_split): [0, ..., len(text)]."""
+    cuts = (C.c_uint64 * (max_pieces + 1))()
+    n = C.c_uint32(0)
+    _check(lib().cls_fastq_split(text, len(text), max_pieces, cuts, C.byref(n)))
+    return [int(c) for c in cuts[: n.value + 1]]
 
 
 def build_kmers(nodes: np.ndarray, bases: np.ndarray, offsets: np.ndarray, leaf_ids: np.ndarray, k: int, m: int, *,
@@ -354,6 +404,25 @@ class PlacementDb:
         recs = C.c_void_p()
         pp = C.byref(params) if params is not None else None
         _check(lib().cls_place_fasta_text(self._h, text, len(text), pp, C.byref(f), C.byref(recs)))
+        try:
+            n = f.n
+            hoff = np.ctypeslib.as_array(f.header_off, shape=(n + 1,)).copy()
+            hraw = C.string_at(f.headers, int(hoff[-1]))
+            headers = [hraw[int(hoff[i]) : int(hoff[i + 1])] for i in range(n)]
+            out = np.frombuffer(C.string_at(recs, n * 24), dtype=_abi.PLACEMENT_DTYPE).copy() if n else np.zeros(0, _abi.PLACEMENT_DTYPE)
+            return headers, out, bool(f.truncated)
+        finally:
+            lib().cls_fasta_free(C.byref(f))
+            lib().cls_host_free(recs)
+
+    def place_fastq_text(self, text: bytes, params: Optional[_abi.Params] = None, trim_5p: int = 0, trim_3p: int = 0):
+        """FASTQ text -> (headers, records, truncated), parsed and quality-trimmed on the device and placed there
+        (cls_place_fastq_text)."""
+        f = _abi.Fasta()
+        recs = C.c_void_p()
+        pp = C.byref(params) if params is not None else None
+        o = _fastq_opts(trim_5p, trim_3p)
+        _check(lib().cls_place_fastq_text(self._h, text, len(text), pp, C.byref(o), C.byref(f), C.byref(recs)))
         try:
             n = f.n
             hoff = np.ctypeslib.as_array(f.header_off, shape=(n + 1,)).copy()
@@ -535,14 +604,31 @@ class Tree:
 
 
 def place_sequences(db, tree: Tree, query_path: str, out_file: str, params: Optional[_abi.Params] = None,
-                    overwrite: bool = False, fmt: int = FORMAT_YAML):
+                    overwrite: bool = False, fmt: int = FORMAT_YAML, query_format: str = "fasta", trim_quality=None):
     """The whole use-case (mod.rs:43-270) through cls_place_sequences, or cls_place_sequences_group when `db` is a
-    PlacementDbGroup: -> (records read, seconds)."""
+    PlacementDbGroup: -> (records read, seconds).  `query_format` "fastq": strict four-line FASTQ, quality-trimmed by
+    `trim_quality` (cutadapt's -q: a 3' cutoff, or a (5', 3') pair; None: no trimming), through the _ex entries."""
+    if query_format not in ("fasta", "fastq"):
+        raise ValueError(f"query_format must be 'fasta' or 'fastq', not {query_format!r}")
+    if trim_quality is not None and query_format != "fastq":
+        raise ValueError("trim_quality needs query_format='fastq'")
     n, sec = C.c_uint32(0), C.c_double(0)
-    fn = lib().cls_place_sequences_group if isinstance(db, PlacementDbGroup) else lib().cls_place_sequences
-    _check_host(fn(db._h, tree._h, query_path.encode(), out_file.encode(),
-                                          C.byref(params) if params is not None else None, 1 if overwrite else 0, fmt,
-                                          C.byref(n), C.byref(sec)))
+    group = isinstance(db, PlacementDbGroup)
+    pp = C.byref(params) if params is not None else None
+    if query_format == "fasta":
+        fn = lib().cls_place_sequences_group if group else lib().cls_place_sequences
+        _check_host(fn(db._h, tree._h, query_path.encode(), out_file.encode(), pp, 1 if overwrite else 0, fmt, C.byref(n), C.byref(sec)))
+        return n.value, sec.value
+    if trim_quality is None:
+        c5, c3 = 0, 0
+    elif isinstance(trim_quality, int):
+        c5, c3 = 0, trim_quality
+    else:
+        c5, c3 = trim_quality
+    o = _fastq_opts(c5, c3)
+    fn = lib().cls_place_sequences_group_ex if group else lib().cls_place_sequences_ex
+    _check_host(fn(db._h, tree._h, query_path.encode(), out_file.encode(), pp, 1 if overwrite else 0, fmt, _abi.QUERY_FASTQ, C.byref(o),
+                   C.byref(n), C.byref(sec)))
     return n.value, sec.value
 
 

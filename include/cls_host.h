@@ -85,6 +85,18 @@ int cls_place_sequences(cls_db* db, const cls_tree* t, const char* query_path, c
 int cls_place_sequences_group(cls_db_group* g, const cls_tree* t, const char* query_path, const char* out_file,
                               const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds);
 
+/* The same two use-cases for either query format.  CLS_QUERY_FASTA: exactly cls_place_sequences[_group] (`fastq`
+ * must then be NULL or all zero).  CLS_QUERY_FASTQ: the query is strict four-line FASTQ (cls_place.h), parsed and
+ * quality-trimmed by `fastq` (NULL: no trimming) on the device with cls_place_fastq_text; the group form cuts the
+ * text with cls_fastq_split.  The output stage is the same for both formats. */
+enum { CLS_QUERY_FASTA = 0, CLS_QUERY_FASTQ = 1 };
+int cls_place_sequences_ex(cls_db* db, const cls_tree* t, const char* query_path, const char* out_file, const cls_params* params,
+                           int overwrite, int format, int query_format, const cls_fastq_opts* fastq, uint32_t* n_placed,
+                           double* seconds);
+int cls_place_sequences_group_ex(cls_db_group* g, const cls_tree* t, const char* query_path, const char* out_file,
+                                 const cls_params* params, int overwrite, int format, int query_format,
+                                 const cls_fastq_opts* fastq, uint32_t* n_placed, double* seconds);
+
 const char* cls_host_last_error(void);
 
 #ifdef __cplusplus

@@ -389,6 +389,51 @@ int cls_fasta_parse_gpu(const char* text, size_t len, int device, cls_fasta* out
 int cls_place_fasta_text(cls_db* db, const char* text, size_t len, const cls_params* params, cls_fasta* fa,
                          cls_placement** records);
 
+/* ---- FASTQ input stage, with quality trimming ------------------------------
+ * Input: strict four-line FASTQ.  Lines end in "\n" or "\r\n" (the '\r' is stripped, as in the FASTA stage; a '\r'
+ * that ends the text without a '\n' is kept); the last line may lack its newline.  A line exists iff it starts
+ * before the end of the text.  Record r is lines 4r .. 4r+3, by line index alone, whatever the lines hold (a quality
+ * line that starts with '@' or '+' is a quality line):
+ *   1. "@header"   2. the sequence line   3. "+" and anything after it   4. the quality line
+ * Record r is well-formed iff all four lines exist, line 1 starts with '@', the header (line 1 without its '@') is
+ * non-empty and valid UTF-8, line 3 starts with '+', the sequence line is ASCII, and the quality line has as many
+ * bytes as the sequence line, each in '!'..'~' (Phred+33).  Multi-line FASTQ shows up as a malformed record.
+ * The parse emits records 0, 1, .. and stops at the first record that is not well-formed:
+ *   - its line 1 is empty and every line from there on is empty: the text ends there cleanly (trailing blank lines);
+ *   - otherwise (malformed, incomplete, or an empty line followed by a non-empty one): that record and everything
+ *     after it are dropped and `truncated` = 1 (callers ignore it, like the FASTA stage's stop, mod.rs:119).
+ * Quality trimming (the BWA / cutadapt `-q` rule), with q[i] = qual[i] - 33, L = the read length, and the cutoffs
+ * c5 = trim_5p, c3 = trim_3p (0: that end is not trimmed; a cutoff above 93 acts like 94: every base goes):
+ *   start: s = 0, best = 0, start = 0; for i = 0 .. L-1:   s += c5 - q[i]; if s < 0 stop; if s > best: best = s, start = i + 1
+ *   stop:  s = 0, best = 0, stop = L;  for i = L-1 .. 0:   s += c3 - q[i]; if s < 0 stop; if s > best: best = s, stop = i
+ *   start >= stop: the read is trimmed to empty; it is still emitted (and placed like an empty FASTA record).
+ * Bases: the kept window [start, stop) of the sequence line, upper-cased, ACGT only (the FASTA filter,
+ * sequence.rs:47-56).  Header bytes are kept as they are (a '>' included).
+ * With both cutoffs 0, a well-formed text parses to the records of the FASTA stage on ">" header "\n" sequence "\n"
+ * per record (headers without '>'), except that FASTA drops an empty last record (file_or_stdin.rs:111-113). */
+typedef struct cls_fastq_opts {
+    uint32_t trim_5p;         /* c5: 5' quality cutoff (0: off)                 */
+    uint32_t trim_3p;         /* c3: 3' quality cutoff (0: off)                 */
+    uint32_t reserved[6];     /* must be 0 (room for later options, 0 = off)    */
+} cls_fastq_opts;             /* NULL wherever a `const cls_fastq_opts*` is taken: no trimming */
+
+/* Host, sequential: the statement of the rules above.  Output as cls_fasta_parse (release with cls_fasta_free). */
+int cls_fastq_parse(const char* text, size_t len, const cls_fastq_opts* opts, cls_fasta* out);
+/* Host only: cut points as cls_fasta_split (same array contract).  A safe cut is the start of a record (a line
+ * index that is a multiple of 4) whose preceding record is well-formed.  Concatenating the pieces' records, up to
+ * and including the first piece that reports `truncated`, gives the records of the whole text. */
+int cls_fastq_split(const char* text, size_t len, uint32_t max_pieces, uint64_t* cuts, uint32_t* n_pieces);
+/* The same stage as data-parallel passes on the device, output as cls_fasta_scan_device (release with
+ * cls_fasta_dev_free).  Synchronises `hip_stream` to learn the line count and the output sizes; the outputs are
+ * complete in stream order on `hip_stream`. */
+int cls_fastq_scan_device(const void* d_text, uint64_t len, const cls_fastq_opts* opts, cls_fasta_dev* out, void* hip_stream);
+/* Host text in, host records out, through the device passes on `device` (-1: current). */
+int cls_fastq_parse_gpu(const char* text, size_t len, const cls_fastq_opts* opts, int device, cls_fasta* out);
+/* The FASTQ twin of cls_place_fasta_text: H2D of the file, the device FASTQ stage, placement on its output, D2H of
+ * the records and headers (same outputs, same ownership). */
+int cls_place_fastq_text(cls_db* db, const char* text, size_t len, const cls_params* params, const cls_fastq_opts* opts,
+                         cls_fasta* fa, cls_placement** records);
+
 /* Experiment knobs (grid sizes, locality-key definition, kernel family; none changes a result; names in
  * csrc/cls_tuning.h are the CLS_* variables in lower case without the prefix, e.g. "no_order").  Process-global,
  * meant for A/B runs: the library itself never reads the environment.  cls_tuning_from_env() takes every knob
