@@ -254,4 +254,11 @@ PLACEMENT_DTYPE = np.dtype(
 STATS_DTYPE = np.dtype(
     [("n_query_kmers", "<u4"), ("n_matched", "<u4"), ("n_with_root", "<u4"), ("index_bytes", "<u4"), ("leaf_postings", "<u8")]
 )
+# clade tally (cls_tally_row, cls_tally_totals)
+TALLY_ROW_DTYPE = np.dtype(
+    [("id", "<u8"), ("n_clade", "<u8"), ("n_direct", "<u8"), ("n_identity", "<u8"), ("n_max_resolution", "<u8"), ("n_inconclusive", "<u8"),
+     ("sum_one", "<i8"), ("sum_rest", "<i8")]
+)
+TALLY_TOTALS_DTYPE = np.dtype([("n_reads", "<u8"), ("status_count", "<u8", (12,)), ("n_unknown_clade", "<u8"), ("n_bad_status", "<u8")])
 assert NODE_DTYPE.itemsize == 32 and PLACEMENT_DTYPE.itemsize == 24 and STATS_DTYPE.itemsize == 24
+assert TALLY_ROW_DTYPE.itemsize == 64 and TALLY_TOTALS_DTYPE.itemsize == 120

@@ -18,6 +18,7 @@
 #include "cls_device.h"
 #include "cls_kernels.h"
 #include "cls_place.h"
+#include "cls_tally.h"
 #include "cls_tuning.h"
 
 namespace {
@@ -108,6 +109,8 @@ struct cls_db {
     std::vector<TimedPair> timed;
     uint64_t ws_seq = 0;
     std::vector<CallSlot> calls;  // host-buffer calls: stream + staging buffers (ws_mu)
+    struct TreeRow { uint64_t id; uint32_t pre, size; };
+    std::vector<TreeRow> tree_rows;  // per row of the descriptor's node table (the clade tally reports in that order)
 };
 
 // ---- experiment knobs (csrc/cls_tuning.h) ------------------------------------------------------------------
@@ -126,7 +129,7 @@ const Knob KNOBS[] = {
     {"order_windows", &cls::Tuning::order_windows}, {"order_both_strands", &cls::Tuning::order_both_strands},
     {"order_block_shift", &cls::Tuning::order_block_shift}, {"order_sample_shift", &cls::Tuning::order_sample_shift},
     {"profile_stop", &cls::Tuning::profile_stop}, {"timing", &cls::Tuning::timing},
-    {"build_full_key", &cls::Tuning::build_full_key},
+    {"build_full_key", &cls::Tuning::build_full_key}, {"tally_no_wave_combine", &cls::Tuning::tally_no_wave_combine},
 };
 }  // namespace
 
@@ -209,9 +212,12 @@ static int upload(const cls::EncodedDb& E, uint32_t n_buckets, int device, cls_d
     CLS_HIP(hipSetDevice(device));
     hipDeviceProp_t prop;
     CLS_HIP(hipGetDeviceProperties(&prop, device));
+    std::vector<cls_db::TreeRow> tree_rows(E.nodes.size());
+    for (size_t r = 0; r < E.nodes.size(); ++r) tree_rows[E.desc_row[r]] = {E.nodes[r].id, E.nodes[r].pre, E.nodes[r].size};
     cls_db* db = new cls_db();
     db->device = device;
     db->n_cu = prop.multiProcessorCount;
+    db->tree_rows = std::move(tree_rows);
     auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
         hipError_t e = hipMalloc(dst, bytes + 64);  // (tail pad: the kernels read node records in pairs and 16-byte entries speculatively)
         if (e != hipSuccess) return e;
@@ -864,16 +870,335 @@ extern "C" int cls_place_batch_group(cls_db_group* g, const char* bases, const u
     }
 }
 
+// ---- clade tally (include/cls_place.h; kernels in cls_tally.hip) ----------------------------------------------------
+
+struct cls_tally {
+    cls_db* db = nullptr;
+    cls::TallyDev dev{};
+    void* d_table = nullptr;
+    void* d_acc = nullptr;        // cnt[3 n] | sums[2 n] | totals[16], 8 bytes each: one memset zeroes the tally
+    void* d_work = nullptr;       // prefix[n + 1] | clade[n]
+    void* d_size = nullptr;
+    void* d_tmp = nullptr;
+    size_t acc_bytes = 0;
+    hipStream_t stream = nullptr; // read-out, reset and the host-record adds
+    std::mutex mu;
+    struct Mark { hipStream_t stream; hipEvent_t ev; };
+    std::vector<Mark> marks;      // per caller stream: an event behind its last add (cls_tally_read waits for them)
+};
+constexpr size_t MAX_TALLY_MARKS = 64;
+
+namespace {
+// RAII: the handle's device current for the scope
+struct DeviceScope {
+    int prev = -1;
+    bool switched = false;
+    hipError_t enter(int device) {
+        hipError_t e = hipGetDevice(&prev);
+        if (e != hipSuccess) return e;
+        if (prev != device) { e = hipSetDevice(device); switched = e == hipSuccess; }
+        return e;
+    }
+    ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
+};
+
+// every add launched so far has finished (t->mu held)
+int tally_drain(cls_tally* t) {
+    for (auto& m : t->marks) CLS_HIP(hipEventSynchronize(m.ev));
+    return CLS_OK;
+}
+
+}  // namespace
+
+extern "C" void cls_tally_destroy(cls_tally* t) {
+    if (!t) return;
+    DeviceScope ds;
+    (void)ds.enter(t->db->device);
+    for (auto& m : t->marks) { (void)hipEventSynchronize(m.ev); (void)hipEventDestroy(m.ev); }
+    if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
+    for (void* p : {t->d_table, t->d_acc, t->d_work, t->d_size, t->d_tmp}) if (p) (void)hipFree(p);
+    delete t;
+}
+
+extern "C" int cls_tally_create(cls_db* db, cls_tally** out) {
+    if (!db || !out) return fail(CLS_E_INVALID_ARG, "cls_tally_create: null argument");
+    *out = nullptr;
+    cls_tally* t = nullptr;
+    try {
+        const uint32_t n = (uint32_t)db->tree_rows.size();
+        if (n == 0 || n >= cls::TALLY_MAX_NODES) return fail(CLS_E_INVALID_ARG, "cls_tally_create: the tree has too many clades for a tally");
+        uint32_t cap = 16;
+        while (cap < 2 * n) cap *= 2;
+        std::vector<cls::IdSlot> table(cap, cls::IdSlot{0, cls::TALLY_NO_PRE, 0});
+        std::vector<uint32_t> size_by_pre(n);
+        for (const auto& r : db->tree_rows) {
+            uint32_t h = (uint32_t)cls::tally_hash(r.id) & (cap - 1);
+            while (table[h].pre != cls::TALLY_NO_PRE) h = (h + 1) & (cap - 1);
+            table[h].id = r.id;
+            table[h].pre = r.pre;
+            size_by_pre[r.pre] = r.size;
+        }
+        DeviceScope ds;
+        CLS_HIP(ds.enter(db->device));
+        t = new cls_tally();
+        t->db = db;
+        t->acc_bytes = (5 * (size_t)n + cls::TALLY_TOTALS) * 8;
+        const size_t tmp_bytes = cls::tally_scan_tmp_bytes(n);
+        hipError_t e;
+        if ((e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)) != hipSuccess ||
+            (e = hipMalloc(&t->d_table, (size_t)cap * sizeof(cls::IdSlot))) != hipSuccess ||
+            (e = hipMalloc(&t->d_acc, t->acc_bytes)) != hipSuccess ||
+            (e = hipMalloc(&t->d_work, (2 * (size_t)n + 1) * 8)) != hipSuccess ||
+            (e = hipMalloc(&t->d_size, (size_t)n * 4)) != hipSuccess ||
+            (e = hipMalloc(&t->d_tmp, tmp_bytes)) != hipSuccess ||
+            (e = hipMemcpyAsync(t->d_table, table.data(), (size_t)cap * sizeof(cls::IdSlot), hipMemcpyHostToDevice, t->stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(t->d_size, size_by_pre.data(), (size_t)n * 4, hipMemcpyHostToDevice, t->stream)) != hipSuccess ||
+            (e = hipMemsetAsync(t->d_acc, 0, t->acc_bytes, t->stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(t->stream)) != hipSuccess) {
+            cls_tally_destroy(t);
+            return fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string("cls_tally_create: ") + hipGetErrorString(e));
+        }
+        cls::TallyDev& d = t->dev;
+        d.table = (const cls::IdSlot*)t->d_table;
+        d.table_mask = cap - 1;
+        d.n_nodes = n;
+        d.cnt = (unsigned long long*)t->d_acc;
+        d.sums = (long long*)t->d_acc + 3 * (size_t)n;
+        d.totals = (unsigned long long*)t->d_acc + 5 * (size_t)n;
+        d.size_by_pre = (const uint32_t*)t->d_size;
+        d.prefix = (unsigned long long*)t->d_work;
+        d.clade = (unsigned long long*)t->d_work + (size_t)n + 1;
+        d.scan_tmp = t->d_tmp;
+        d.scan_tmp_bytes = tmp_bytes;
+        *out = t;
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        cls_tally_destroy(t);
+        return fail(CLS_E_NOMEM, "cls_tally_create: out of host memory");
+    } catch (...) {
+        cls_tally_destroy(t);
+        return fail(CLS_E_INTERNAL, "cls_tally_create: unknown exception");
+    }
+}
+
+extern "C" int cls_tally_reset(cls_tally* t) {
+    if (!t) return fail(CLS_E_INVALID_ARG, "cls_tally_reset: null handle");
+    DeviceScope ds;
+    CLS_HIP(ds.enter(t->db->device));
+    std::lock_guard<std::mutex> g(t->mu);
+    if (int rc = tally_drain(t)) return rc;
+    CLS_HIP(hipMemsetAsync(t->d_acc, 0, t->acc_bytes, t->stream));
+    CLS_HIP(hipStreamSynchronize(t->stream));
+    return CLS_OK;
+}
+
+// The add on `stream` (the handle's device is current), and the mark cls_tally_read waits for.
+// `mark` = false: the caller synchronises `stream` itself before it returns.
+static int tally_add_on(cls_tally* t, const void* d_records, uint32_t n, hipStream_t stream, bool mark = true) {
+    if (((uintptr_t)d_records & 7) != 0) return fail(CLS_E_INVALID_ARG, "cls_tally_add_device: records must be 8-byte aligned");
+    std::lock_guard<std::mutex> g(t->mu);
+    CLS_HIP(cls::launch_tally_add(t->dev, d_records, n, (uint32_t)t->db->n_cu, cls::tuning().tally_no_wave_combine ? 0 : 1, stream));
+    if (!mark) return CLS_OK;
+    // (hipStreamPerThread is one handle value that names a different stream in every host thread: never cached)
+    if (stream != hipStreamPerThread) {
+        for (auto& m : t->marks)
+            if (m.stream == stream) { CLS_HIP(hipEventRecord(m.ev, stream)); return CLS_OK; }
+        if (t->marks.size() < MAX_TALLY_MARKS) {
+            hipEvent_t ev = nullptr;
+            CLS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            if (hipEventRecord(ev, stream) != hipSuccess) { (void)hipEventDestroy(ev); return fail(CLS_E_HIP, "cls_tally_add_device: hipEventRecord failed"); }
+            t->marks.push_back({stream, ev});
+            return CLS_OK;
+        }
+    }
+    CLS_HIP(hipStreamSynchronize(stream));  // no mark to leave: the add is waited for here
+    return CLS_OK;
+}
+
+extern "C" int cls_tally_add_device(cls_tally* t, const void* d_records, uint32_t n, void* hip_stream) {
+    if (!t) return fail(CLS_E_INVALID_ARG, "cls_tally_add_device: null handle");
+    if (n == 0) return CLS_OK;
+    if (!d_records) return fail(CLS_E_INVALID_ARG, "cls_tally_add_device: null buffer");
+    DeviceScope ds;
+    CLS_HIP(ds.enter(t->db->device));
+    try {
+        return tally_add_on(t, d_records, n, (hipStream_t)hip_stream);
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_tally_add_device: unknown exception");
+    }
+}
+
+extern "C" int cls_tally_add(cls_tally* t, const cls_placement* records, uint32_t n) {
+    if (!t) return fail(CLS_E_INVALID_ARG, "cls_tally_add: null handle");
+    if (n == 0) return CLS_OK;
+    if (!records) return fail(CLS_E_INVALID_ARG, "cls_tally_add: null buffer");
+    DeviceScope ds;
+    CLS_HIP(ds.enter(t->db->device));
+    void* d = nullptr;
+    hipError_t e = hipMalloc(&d, (size_t)n * sizeof(cls_placement));
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string("cls_tally_add: ") + hipGetErrorString(e));
+    int rc = CLS_OK;
+    try {
+        if ((e = hipMemcpyAsync(d, records, (size_t)n * sizeof(cls_placement), hipMemcpyHostToDevice, t->stream)) != hipSuccess)
+            rc = fail(CLS_E_HIP, std::string("cls_tally_add: ") + hipGetErrorString(e));
+        else rc = tally_add_on(t, d, n, t->stream);
+    } catch (...) {
+        rc = fail(CLS_E_INTERNAL, "cls_tally_add: unknown exception");
+    }
+    (void)hipStreamSynchronize(t->stream);  // synchronous; the staging copy is freed behind the kernel
+    (void)hipFree(d);
+    return rc;
+}
+
+extern "C" int cls_tally_read(cls_tally* t, cls_tally_row* rows, uint32_t n_rows, cls_tally_totals* totals) {
+    if (!t) return fail(CLS_E_INVALID_ARG, "cls_tally_read: null handle");
+    const uint32_t n = t->dev.n_nodes;
+    if (rows && n_rows != n) return fail(CLS_E_INVALID_ARG, "cls_tally_read: n_rows must be the tree's n_nodes (" + std::to_string(n) + ")");
+    DeviceScope ds;
+    CLS_HIP(ds.enter(t->db->device));
+    try {
+        std::vector<unsigned long long> acc(5 * (size_t)n + cls::TALLY_TOTALS), clade(n);
+        {
+            std::lock_guard<std::mutex> g(t->mu);
+            if (int rc = tally_drain(t)) return rc;
+            if (rows) {
+                CLS_HIP(cls::launch_tally_finish(t->dev, t->stream));
+                CLS_HIP(hipMemcpyAsync(clade.data(), t->dev.clade, (size_t)n * 8, hipMemcpyDeviceToHost, t->stream));
+            }
+            CLS_HIP(hipMemcpyAsync(acc.data(), t->d_acc, t->acc_bytes, hipMemcpyDeviceToHost, t->stream));
+            CLS_HIP(hipStreamSynchronize(t->stream));
+        }
+        if (rows) {
+            const unsigned long long* cnt = acc.data();
+            const long long* sums = (const long long*)acc.data() + 3 * (size_t)n;
+            for (uint32_t i = 0; i < n; ++i) {
+                const auto& tr = t->db->tree_rows[i];
+                cls_tally_row& r = rows[i];
+                r.id = tr.id;
+                r.n_clade = clade[tr.pre];
+                r.n_identity = cnt[3 * (size_t)tr.pre];
+                r.n_max_resolution = cnt[3 * (size_t)tr.pre + 1];
+                r.n_inconclusive = cnt[3 * (size_t)tr.pre + 2];
+                r.n_direct = r.n_identity + r.n_max_resolution + r.n_inconclusive;
+                r.sum_one = sums[2 * (size_t)tr.pre];
+                r.sum_rest = sums[2 * (size_t)tr.pre + 1];
+            }
+        }
+        if (totals) {
+            const unsigned long long* tot = acc.data() + 5 * (size_t)n;
+            memset(totals, 0, sizeof *totals);
+            for (int s = 0; s < 12; ++s) { totals->status_count[s] = tot[s]; totals->n_reads += tot[s]; }
+            totals->n_bad_status = tot[cls::TALLY_BAD];
+            totals->n_unknown_clade = tot[cls::TALLY_UNKNOWN];
+            totals->n_reads += totals->n_bad_status;
+        }
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CLS_E_NOMEM, "cls_tally_read: out of host memory");
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_tally_read: unknown exception");
+    }
+}
+
+extern "C" int cls_tally_merge(cls_tally_row* rows, cls_tally_totals* totals, const cls_tally_row* add_rows,
+                               const cls_tally_totals* add_totals, uint32_t n_rows) {
+    if ((n_rows && (!rows || !add_rows)) || (!totals != !add_totals)) return fail(CLS_E_INVALID_ARG, "cls_tally_merge: null argument");
+    for (uint32_t i = 0; i < n_rows; ++i) {
+        const bool fresh = rows[i].id == 0 && rows[i].n_clade == 0 && rows[i].n_direct == 0;
+        if (!fresh && rows[i].id != add_rows[i].id) return fail(CLS_E_INVALID_ARG, "cls_tally_merge: row " + std::to_string(i) + " names different clades");
+    }
+    for (uint32_t i = 0; i < n_rows; ++i) {
+        cls_tally_row& r = rows[i];
+        const cls_tally_row& a = add_rows[i];
+        r.id = a.id;
+        r.n_clade += a.n_clade; r.n_direct += a.n_direct; r.n_identity += a.n_identity;
+        r.n_max_resolution += a.n_max_resolution; r.n_inconclusive += a.n_inconclusive;
+        r.sum_one += a.sum_one; r.sum_rest += a.sum_rest;
+    }
+    if (totals) {
+        totals->n_reads += add_totals->n_reads;
+        for (int s = 0; s < 12; ++s) totals->status_count[s] += add_totals->status_count[s];
+        totals->n_unknown_clade += add_totals->n_unknown_clade;
+        totals->n_bad_status += add_totals->n_bad_status;
+    }
+    return CLS_OK;
+}
+
+// The counting rules as they are written in cls_place.h, one record after the other: a sorted id -> row list, the
+// direct counters per row, then the call's n_direct summed bottom-up over the rows in reverse breadth-first order.
+extern "C" int cls_tally_host(const cls_node* nodes, uint32_t n_nodes, const cls_placement* records, uint64_t n,
+                              cls_tally_row* rows, cls_tally_totals* totals) {
+    if (!nodes || n_nodes == 0 || !rows || !totals || (!records && n)) return fail(CLS_E_INVALID_ARG, "cls_tally_host: null argument");
+    try {
+        // parent row of every row, from the child ranges (`parent` ids are informational); row 0 is the root
+        std::vector<uint32_t> parent_row(n_nodes, UINT32_MAX);
+        std::vector<std::pair<uint64_t, uint32_t>> by_id(n_nodes);
+        for (uint32_t r = 0; r < n_nodes; ++r) {
+            by_id[r] = {nodes[r].id, r};
+            if (nodes[r].n_children == 0) continue;
+            if ((uint64_t)nodes[r].first_child + nodes[r].n_children > n_nodes || nodes[r].first_child == 0)
+                return fail(CLS_E_BAD_TREE, "cls_tally_host: child rows out of range");
+            for (uint32_t c = nodes[r].first_child; c < nodes[r].first_child + nodes[r].n_children; ++c) {
+                if (parent_row[c] != UINT32_MAX) return fail(CLS_E_BAD_TREE, "cls_tally_host: row is the child of two parents (not a tree)");
+                parent_row[c] = r;
+            }
+        }
+        if (parent_row[0] != UINT32_MAX) return fail(CLS_E_BAD_TREE, "cls_tally_host: the root has a parent");
+        for (uint32_t r = 1; r < n_nodes; ++r)
+            if (parent_row[r] == UINT32_MAX) return fail(CLS_E_BAD_TREE, "cls_tally_host: rows unreachable from the root");
+        std::vector<uint32_t> bfs;  // parents before their children
+        bfs.reserve(n_nodes);
+        bfs.push_back(0);
+        for (size_t i = 0; i < bfs.size(); ++i)
+            for (uint32_t c = 0; c < nodes[bfs[i]].n_children; ++c) bfs.push_back(nodes[bfs[i]].first_child + c);
+        if (bfs.size() != n_nodes) return fail(CLS_E_BAD_TREE, "cls_tally_host: rows unreachable from the root");
+        std::vector<uint64_t> below(n_nodes, 0);  // this call's n_direct, then its subtree sums
+        std::sort(by_id.begin(), by_id.end());
+        for (uint32_t r = 1; r < n_nodes; ++r)
+            if (by_id[r].first == by_id[r - 1].first) return fail(CLS_E_BAD_TREE, "cls_tally_host: duplicate clade id " + std::to_string(by_id[r].first));
+        for (uint32_t r = 0; r < n_nodes; ++r) {
+            if (rows[r].id != nodes[r].id && (rows[r].id != 0 || rows[r].n_clade != 0))
+                return fail(CLS_E_INVALID_ARG, "cls_tally_host: rows[" + std::to_string(r) + "] was filled for another tree");
+            rows[r].id = nodes[r].id;
+        }
+        for (uint64_t i = 0; i < n; ++i) {
+            const cls_placement& p = records[i];
+            totals->n_reads++;
+            if (p.status >= 12) { totals->n_bad_status++; continue; }
+            totals->status_count[p.status]++;
+            if (p.status != CLS_IDENTITY_FOUND && p.status != CLS_MAX_RESOLUTION && p.status != CLS_INCONCLUSIVE) continue;
+            auto it = std::lower_bound(by_id.begin(), by_id.end(), std::make_pair((uint64_t)p.clade_id, (uint32_t)0));
+            if (it == by_id.end() || it->first != p.clade_id) { totals->n_unknown_clade++; continue; }
+            cls_tally_row& r = rows[it->second];
+            r.n_direct++;
+            below[it->second]++;
+            if (p.status == CLS_IDENTITY_FOUND) { r.n_identity++; r.sum_one += p.one; r.sum_rest += p.rest; }
+            else if (p.status == CLS_MAX_RESOLUTION) r.n_max_resolution++;
+            else r.n_inconclusive++;
+        }
+        for (size_t i = n_nodes; i-- > 1;) below[parent_row[bfs[i]]] += below[bfs[i]];
+        for (uint32_t r = 0; r < n_nodes; ++r) rows[r].n_clade += below[r];
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CLS_E_NOMEM, "cls_tally_host: out of host memory");
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_tally_host: unknown exception");
+    }
+}
+
 // Query text -> records, all on the device: H2D of the file bytes, `scan` (the device FASTA or FASTQ stage),
 // placement straight from the scanned bases, D2H of the 24-byte records and of the headers (the output stage needs
 // those on the host).  `fa->bases` / `fa->base_off` come back NULL: the bases never leave the device.  `who` names the
 // entry in messages.
 using ScanText = int (*)(const void* d_text, uint64_t len, const void* opts, cls_fasta_dev* out, hipStream_t stream);
+// With `tally` (the cls_tally_*_text entries) the records are added to it on the device instead: `fa` only carries n and
+// truncated, `records` is NULL, and neither the headers, their offsets nor the records are copied back.
 static int place_text(const char* who, cls_db* db, const char* text, size_t len, const cls_params* params, ScanText scan,
-                      const void* scan_opts, cls_fasta* fa, cls_placement** records) {
-    if (!db || !fa || !records || (!text && len)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": null argument");
+                      const void* scan_opts, cls_fasta* fa, cls_placement** records, cls_tally* tally = nullptr) {
+    if (!db || !fa || (!records && !tally) || (!text && len)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": null argument");
+    if (tally && tally->db != db) return fail(CLS_E_INVALID_ARG, std::string(who) + ": the tally belongs to another handle");
     memset(fa, 0, sizeof *fa);
-    *records = nullptr;
+    if (records) *records = nullptr;
     int prev = 0;
     CLS_HIP(hipGetDevice(&prev));
     CLS_HIP(hipSetDevice(db->device));
@@ -907,13 +1232,15 @@ static int place_text(const char* who, cls_db* db, const char* text, size_t len,
         const uint32_t n = dv.n;
         fa->n = n;
         fa->truncated = dv.truncated;
-        fa->headers = (char*)malloc(dv.n_header_bytes + 1);
-        fa->header_off = (uint64_t*)malloc(((size_t)n + 1) * 8);
-        recs = (cls_placement*)malloc(((size_t)n + 1) * sizeof(cls_placement));
         std::vector<uint64_t> boff((size_t)n + 1);
-        if (!fa->headers || !fa->header_off || !recs) { cleanup(); return fail(CLS_E_NOMEM, std::string(who) + ": out of host memory"); }
-        if (dv.n_header_bytes) CLS_TRY(hipMemcpyAsync(fa->headers, dv.d_headers, dv.n_header_bytes, hipMemcpyDeviceToHost, stream));
-        CLS_TRY(hipMemcpyAsync(fa->header_off, dv.d_header_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
+        if (!tally) {
+            fa->headers = (char*)malloc(dv.n_header_bytes + 1);
+            fa->header_off = (uint64_t*)malloc(((size_t)n + 1) * 8);
+            recs = (cls_placement*)malloc(((size_t)n + 1) * sizeof(cls_placement));
+            if (!fa->headers || !fa->header_off || !recs) { cleanup(); return fail(CLS_E_NOMEM, std::string(who) + ": out of host memory"); }
+            if (dv.n_header_bytes) CLS_TRY(hipMemcpyAsync(fa->headers, dv.d_headers, dv.n_header_bytes, hipMemcpyDeviceToHost, stream));
+            CLS_TRY(hipMemcpyAsync(fa->header_off, dv.d_header_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
+        }
         CLS_TRY(hipMemcpyAsync(boff.data(), dv.d_base_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
         CLS_TRY(hipStreamSynchronize(stream));
         const uint32_t max_reads = 16u << 20;  // bounds the per-call scratch (class lists, sort keys)
@@ -930,10 +1257,13 @@ static int place_text(const char* who, cls_db* db, const char* text, size_t len,
             }
             rc = place_device(db, dv.d_bases, (const uint64_t*)dv.d_base_off + first, cnt, params, d_out, nullptr, stream, (uint32_t)(2 * longest), n_long);
             if (rc != CLS_OK) { cleanup(); return rc; }
-            CLS_TRY(hipMemcpyAsync(recs + first, d_out, (size_t)cnt * sizeof(cls_placement), hipMemcpyDeviceToHost, stream));
+            if (tally) {
+                rc = tally_add_on(tally, d_out, cnt, stream, false);  // (in stream order behind the placement; waited for below)
+                if (rc != CLS_OK) { cleanup(); return rc; }
+            } else CLS_TRY(hipMemcpyAsync(recs + first, d_out, (size_t)cnt * sizeof(cls_placement), hipMemcpyDeviceToHost, stream));
             CLS_TRY(hipStreamSynchronize(stream));
         }
-        *records = recs;
+        if (records) *records = recs;
         ok = true;
         cleanup();
         return CLS_OK;
@@ -962,4 +1292,33 @@ extern "C" int cls_place_fastq_text(cls_db* db, const char* text, size_t len, co
                           return cls_fastq_scan_device(d, n, (const cls_fastq_opts*)o, out, st);
                       },
                       opts, fa, records);
+}
+
+// The same two routes into a tally: nothing per read returns to the host.
+extern "C" int cls_tally_fasta_text(cls_db* db, cls_tally* t, const char* text, size_t len, const cls_params* params,
+                                    uint32_t* n, uint32_t* truncated) {
+    if (!t) return fail(CLS_E_INVALID_ARG, "cls_tally_fasta_text: null tally");
+    cls_fasta fa;
+    const int rc = place_text("cls_tally_fasta_text", db, text, len, params,
+                              [](const void* d, uint64_t m, const void*, cls_fasta_dev* out, hipStream_t st) { return cls_fasta_scan_device(d, m, out, st); },
+                              nullptr, &fa, nullptr, t);
+    if (rc != CLS_OK) return rc;
+    if (n) *n = fa.n;
+    if (truncated) *truncated = fa.truncated;
+    return CLS_OK;
+}
+
+extern "C" int cls_tally_fastq_text(cls_db* db, cls_tally* t, const char* text, size_t len, const cls_params* params,
+                                    const cls_fastq_opts* opts, uint32_t* n, uint32_t* truncated) {
+    if (!t) return fail(CLS_E_INVALID_ARG, "cls_tally_fastq_text: null tally");
+    cls_fasta fa;
+    const int rc = place_text("cls_tally_fastq_text", db, text, len, params,
+                              [](const void* d, uint64_t m, const void* o, cls_fasta_dev* out, hipStream_t st) {
+                                  return cls_fastq_scan_device(d, m, (const cls_fastq_opts*)o, out, st);
+                              },
+                              opts, &fa, nullptr, t);
+    if (rc != CLS_OK) return rc;
+    if (n) *n = fa.n;
+    if (truncated) *truncated = fa.truncated;
+    return CLS_OK;
 }

@@ -128,6 +128,7 @@ int encode_db(const cls_db_desc* d, EncodedDb& E, std::string& err) {
     std::vector<uint32_t> new_row(N);
     for (uint32_t r = 0; r < N; ++r) new_row[order[r]] = r;
     E.nodes.assign(N, DNode{});
+    E.desc_row = order;
     for (uint32_t r = 0; r < N; ++r) {
         const cls_node& n = d->nodes[order[r]];
         DNode& o = E.nodes[r];

@@ -38,6 +38,7 @@ template <class T> using HugeVec = std::vector<T, HugeAlloc<T>>;
 
 struct EncodedDb {
     std::vector<DNode> nodes;
+    std::vector<uint32_t> desc_row;   // engine row -> row of cls_db_desc.nodes (the clade tally reports in the caller's order)
     std::vector<uint32_t> kids;       // 4 words per node: where its 3rd / 4th / 5th child starts (cls_device.h)
     HugeVec<Slot> table;              // FMT_LIST: Slot; FMT_SPLIT: TSlot (same size)
     HugeVec<uint32_t> postings2;      // FMT_SPLIT: the split records again, narrow parts as bit masks (cls_device.h)

@@ -696,11 +696,115 @@ extern "C" int cls_serialize_results(const cls_tree* t, const char* headers, con
 
 extern "C" void cls_host_free(void* p) { free(p); }
 
+extern "C" int cls_tree_nodes(const cls_tree* t, const cls_node** nodes, uint32_t* n_nodes) {
+    if (!t || !nodes || !n_nodes) return fail(CLS_E_INVALID_ARG, "cls_tree_nodes: null argument");
+    *nodes = t->rows.data();
+    *n_nodes = (uint32_t)t->rows.size();
+    return CLS_OK;
+}
+
+// ---- clade report (include/cls_host.h) ------------------------------------------------------------------------------
+static const char* const STATUS_NAMES[12] = {
+    "UNCLASSIFIABLE_NO_MATCH", "UNCLASSIFIABLE_NO_ROOT", "UNCLASSIFIABLE_COVERAGE", "UNCLASSIFIABLE_LEVEL1", "IDENTITY_FOUND",
+    "MAX_RESOLUTION", "INCONCLUSIVE", "ERR_TOO_FEW_KMERS", "ERR_MAX_ITER", "ERR_ROOT_NO_CHILDREN", "ERR_INVALID_BASE",
+    "ERR_READ_TOO_LONG"};
+
+static void report_text(const cls_tree* t, const cls_tally_row* rows, const cls_tally_totals* totals, int all_rows, std::string& o) {
+    char buf[160];
+    o += "# classeq2_amd clade report v1\n";
+    snprintf(buf, sizeof buf, "# reads\t%llu\n", (unsigned long long)totals->n_reads);
+    o += buf;
+    for (int s = 0; s < 12; ++s) {
+        snprintf(buf, sizeof buf, "# status\t%s\t%llu\n", STATUS_NAMES[s], (unsigned long long)totals->status_count[s]);
+        o += buf;
+    }
+    snprintf(buf, sizeof buf, "# unknown_clade\t%llu\n# bad_status\t%llu\n", (unsigned long long)totals->n_unknown_clade,
+             (unsigned long long)totals->n_bad_status);
+    o += buf;
+    o += "clade_id\tparent_id\tkind\tdepth\tname\tn_clade\tn_direct\tn_identity\tn_max_resolution\tn_inconclusive\tmean_one\tmean_rest\n";
+    std::map<const Clade*, uint32_t> row_of;
+    for (uint32_t r = 0; r < t->row_clade.size(); ++r) row_of[t->row_clade[r]] = r;
+    struct Fr { const Clade* c; const Clade* parent; uint32_t depth; };
+    std::vector<Fr> st{{&t->root, nullptr, 0}};
+    static const char* const KINDS[3] = {"ROOT", "NODE", "LEAF"};
+    while (!st.empty()) {
+        const Fr f = st.back();
+        st.pop_back();
+        for (auto it = f.c->children.rbegin(); it != f.c->children.rend(); ++it) st.push_back({&*it, f.c, f.depth + 1});
+        const cls_tally_row& r = rows[row_of[f.c]];
+        if (!all_rows && r.n_clade == 0) continue;
+        o += std::to_string(f.c->id);
+        o += '\t';
+        o += f.parent ? std::to_string(f.parent->id) : std::string("-");
+        o += '\t';
+        o += KINDS[f.c->kind >= 0 && f.c->kind <= 2 ? f.c->kind : 1];
+        o += '\t';
+        o += std::to_string(f.depth);
+        o += '\t';
+        if (f.c->has_name)
+            for (char ch : f.c->name) o += (ch == '\t' || ch == '\n' || ch == '\r') ? ' ' : ch;  // (one line, one field)
+        snprintf(buf, sizeof buf, "\t%llu\t%llu\t%llu\t%llu\t%llu\t", (unsigned long long)r.n_clade, (unsigned long long)r.n_direct,
+                 (unsigned long long)r.n_identity, (unsigned long long)r.n_max_resolution, (unsigned long long)r.n_inconclusive);
+        o += buf;
+        if (r.n_identity) snprintf(buf, sizeof buf, "%.3f\t%.3f\n", (double)r.sum_one / (double)r.n_identity, (double)r.sum_rest / (double)r.n_identity);
+        else snprintf(buf, sizeof buf, "-\t-\n");
+        o += buf;
+    }
+}
+
+static int check_report_rows(const char* who, const cls_tree* t, const cls_tally_row* rows) {
+    for (size_t r = 0; r < t->rows.size(); ++r)
+        if (rows[r].id != t->rows[r].id) return fail(CLS_E_INVALID_ARG, std::string(who) + ": rows[" + std::to_string(r) + "] is not the tree's row");
+    return CLS_OK;
+}
+
+extern "C" int cls_tally_report(const cls_tree* t, const cls_tally_row* rows, const cls_tally_totals* totals, int all_rows,
+                                char** out_text, size_t* out_len) {
+    if (!t || !rows || !totals || !out_text || !out_len) return fail(CLS_E_INVALID_ARG, "cls_tally_report: null argument");
+    try {
+        if (int rc = check_report_rows("cls_tally_report", t, rows)) return rc;
+        std::string o;
+        report_text(t, rows, totals, all_rows, o);
+        *out_text = (char*)malloc(o.size() + 1);
+        if (!*out_text) return fail(CLS_E_NOMEM, "cls_tally_report: out of memory");
+        memcpy(*out_text, o.data(), o.size());
+        (*out_text)[o.size()] = 0;
+        *out_len = o.size();
+        return CLS_OK;
+    } catch (const std::exception& ex) {
+        return fail(CLS_E_INTERNAL, std::string("cls_tally_report: ") + ex.what());
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_tally_report: unknown exception");
+    }
+}
+
+// The report file's overwrite policy (as the result file's, mod.rs:83-96), checked before anything is placed.
+static int check_report_path(const char* report_path, int overwrite) {
+    struct stat sb;
+    if (stat(report_path, &sb) == 0 && !overwrite)
+        return fail(CLS_E_INVALID_ARG, std::string("Could not overwrite existing file \"") + report_path + "\" when overwrite option is `false`.");
+    const std::string p = report_path;
+    const size_t slash = p.find_last_of('/');
+    if (slash != std::string::npos && slash > 0) (void)mkdir(p.substr(0, slash).c_str(), 0777);
+    return CLS_OK;
+}
+
+static int write_report(const cls_tree* t, const cls_tally_row* rows, const cls_tally_totals* totals, int all_rows, const char* report_path) {
+    std::string o;
+    report_text(t, rows, totals, all_rows, o);
+    FILE* f = fopen(report_path, "wb");
+    if (!f) return fail(CLS_E_INVALID_ARG, std::string("Unable to open file ") + report_path);
+    const bool ok = o.empty() || fwrite(o.data(), 1, o.size(), f) == o.size();
+    if (fclose(f) != 0 || !ok) return fail(CLS_E_INTERNAL, "Error writing to file");
+    return CLS_OK;
+}
+
 // The use-case around a placement stage (mod.rs:43-270): output paths and overwrite policy, read the whole input,
 // `place` it (FASTA text -> headers + records), serialise, write.  `who` names the entry in messages.
 using PlaceText = std::function<int(const std::string& text, cls_fasta* fa, cls_placement** recs)>;
 static int place_sequences_with(const char* who, const cls_tree* t, const char* query_path, const char* out_file,
-                                int overwrite, int format, uint32_t* n_placed, double* seconds, const PlaceText& place) {
+                                int overwrite, int format, uint32_t* n_placed, double* seconds, const PlaceText& place,
+                                const char* report_path = nullptr, int all_rows = 0) {
     // released on every way out, a throwing read_file / serialize_pieces included
     struct Guard {
         FILE *fo = nullptr, *fe = nullptr;
@@ -709,6 +813,7 @@ static int place_sequences_with(const char* who, const cls_tree* t, const char* 
         ~Guard() { if (fo) fclose(fo); if (fe) fclose(fe); free(recs); cls_fasta_free(&fa); }
     } g;
     try {
+        if (report_path) if (int rc = check_report_path(report_path, overwrite)) return rc;
         // ---- output paths + overwrite policy (mod.rs:73-106) ------------------------------------------
         const std::string out_path = with_extension(out_file, format == CLS_FORMAT_YAML ? "yaml" : "jsonl");
         const std::string err_path = with_extension(out_file, "error");
@@ -739,6 +844,14 @@ static int place_sequences_with(const char* who, const cls_tree* t, const char* 
         auto t2 = std::chrono::steady_clock::now();
         std::vector<std::string> po, pe;  // the pieces go to the files as they are: no second copy of 300 MB of text
         serialize_pieces(t, fa.headers, fa.header_off, fa.n, recs, format, po, pe);
+        if (report_path) {  // the clade report of the same records, counted on the host
+            std::vector<cls_tally_row> rows(t->rows.size(), cls_tally_row{});
+            cls_tally_totals totals{};
+            rc = cls_tally_host(t->rows.data(), (uint32_t)t->rows.size(), recs, fa.n, rows.data(), &totals);
+            if (rc != CLS_OK) return fail(rc, cls_last_error());
+            rc = write_report(t, rows.data(), &totals, all_rows, report_path);
+            if (rc != CLS_OK) return rc;
+        }
         free(recs);
         recs = nullptr;
         auto t3 = std::chrono::steady_clock::now();
@@ -895,4 +1008,148 @@ extern "C" int cls_place_sequences_group(cls_db_group* grp, const cls_tree* t, c
                                          const cls_params* params, int overwrite, int format, uint32_t* n_placed, double* seconds) {
     return cls_place_sequences_group_ex(grp, t, query_path, out_file, params, overwrite, format, CLS_QUERY_FASTA, nullptr, n_placed,
                                         seconds);
+}
+
+extern "C" int cls_place_sequences_report(cls_db* db, cls_db_group* grp, const cls_tree* t, const char* query_path, const char* out_file,
+                                          const cls_params* params, int overwrite, int format, int query_format,
+                                          const cls_fastq_opts* fastq, const char* report_path, int all_rows, uint32_t* n_placed,
+                                          double* seconds) {
+    if ((!db == !grp) || !t || !query_path || !out_file || !report_path) return fail(CLS_E_INVALID_ARG, "cls_place_sequences_report: null argument (one of db, g)");
+    QueryFormat q;
+    if (int rc = check_query_format("cls_place_sequences_report", query_format, fastq, &q)) return rc;
+    return place_sequences_with("cls_place_sequences_report", t, query_path, out_file, overwrite, format, n_placed, seconds,
+                                [&](const std::string& text, cls_fasta* fa, cls_placement** recs) {
+                                    if (grp) return place_text_group(grp, text, params, q, fa, recs);
+                                    int rc = place_text_one(db, text.data(), text.size(), params, q, fa, recs);
+                                    if (rc != CLS_OK) { std::string m = cls_last_error(); return fail(rc, m); }
+                                    return CLS_OK;
+                                },
+                                report_path, all_rows);
+}
+
+// ---- query file -> clade report through device tallies ----------------------------------------------------------------
+static constexpr uint64_t DEFAULT_PIECE_BYTES = 64ull << 20;
+static constexpr uint64_t MAX_PIECES = 1u << 20;
+
+// `dbs`: one handle (cls_profile_sequences) or the replicas of a group.
+static int profile_with(const char* who, const std::vector<cls_db*>& dbs, const cls_tree* t, const char* query_path, const char* report_path,
+                        const cls_params* params, int overwrite, int query_format, const cls_fastq_opts* fastq, uint64_t piece_bytes,
+                        int all_rows, uint32_t* n_placed, double* seconds) {
+    QueryFormat q;
+    if (int rc = check_query_format(who, query_format, fastq, &q)) return rc;
+    struct Tallies {
+        std::vector<cls_tally*> v;
+        ~Tallies() { for (cls_tally* x : v) cls_tally_destroy(x); }
+    } tallies;
+    try {
+        if (int rc = check_report_path(report_path, overwrite)) return rc;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::string text;
+        if (strcmp(query_path, "-") == 0) { std::stringstream ss; ss << std::cin.rdbuf(); text = ss.str(); }
+        else text = read_file(query_path);
+        if (piece_bytes == 0) piece_bytes = DEFAULT_PIECE_BYTES;
+        const uint32_t max_pieces = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(MAX_PIECES, (text.size() + piece_bytes - 1) / piece_bytes));
+        std::vector<uint64_t> cuts((size_t)max_pieces + 1);
+        uint32_t n_pieces = 0;
+        const bool fq = q.kind == CLS_QUERY_FASTQ;
+        int rc = (fq ? cls_fastq_split : cls_fasta_split)(text.data(), text.size(), max_pieces, cuts.data(), &n_pieces);
+        if (rc != CLS_OK) return fail(rc, std::string(who) + (fq ? ": cls_fastq_split failed" : ": cls_fasta_split failed"));
+        const uint32_t n_rep = (uint32_t)dbs.size();
+        for (uint32_t i = 0; i < n_rep; ++i) {
+            cls_tally* x = nullptr;
+            if ((rc = cls_tally_create(dbs[i], &x)) != CLS_OK) return fail(rc, cls_last_error());
+            tallies.v.push_back(x);
+        }
+        struct Piece { int rc = CLS_OK; uint32_t n = 0, truncated = 0; bool done = false; std::string msg; };
+        std::vector<Piece> pieces(n_pieces);
+        // pieces [0, upto) dealt to the replicas, replica i on a thread of its own (one replica: the calling thread)
+        auto run = [&](uint32_t upto) {
+            auto work = [&](uint32_t rep) {
+                for (uint32_t i = rep; i < upto; i += n_rep) {
+                    Piece& p = pieces[i];
+                    const char* piece = text.data() + cuts[i];
+                    const size_t len = cuts[i + 1] - cuts[i];
+                    p.rc = fq ? cls_tally_fastq_text(dbs[rep], tallies.v[rep], piece, len, params, &q.fastq, &p.n, &p.truncated)
+                              : cls_tally_fasta_text(dbs[rep], tallies.v[rep], piece, len, params, &p.n, &p.truncated);
+                    p.done = true;
+                    if (p.rc != CLS_OK) { p.msg = cls_last_error(); return; }
+                    if (p.truncated && n_rep == 1) return;  // (in order on one replica: nothing after it is tallied)
+                }
+            };
+            if (n_rep == 1) { work(0); return; }
+            std::vector<std::thread> th;
+            try {
+                for (uint32_t r = 0; r < n_rep; ++r) th.emplace_back(work, r);
+            } catch (...) {
+                for (uint32_t i = 0; i < upto; ++i) if (!pieces[i].done) { pieces[i].rc = CLS_E_INTERNAL; pieces[i].msg = "worker thread not started"; }
+            }
+            for (auto& x : th) x.join();
+        };
+        auto first_stop = [&](uint32_t upto) {  // the first piece that failed or stopped early, or `upto`
+            for (uint32_t i = 0; i < upto; ++i)
+                if (pieces[i].rc != CLS_OK || pieces[i].truncated) return i;
+            return upto;
+        };
+        run(n_pieces);
+        uint32_t stop = first_stop(n_pieces);
+        if (stop < n_pieces && pieces[stop].rc == CLS_OK) {
+            bool beyond = false;
+            for (uint32_t i = stop + 1; i < n_pieces; ++i) beyond |= pieces[i].done;
+            if (beyond) {
+                // the replicas ran ahead of the piece that stops early: count again, only the pieces up to and including it
+                for (cls_tally* x : tallies.v) if ((rc = cls_tally_reset(x)) != CLS_OK) return fail(rc, cls_last_error());
+                pieces.assign(n_pieces, Piece());
+                run(stop + 1);
+                stop = first_stop(stop + 1);
+            }
+        }
+        if (stop < n_pieces && pieces[stop].rc != CLS_OK)
+            return fail(pieces[stop].rc, std::string(who) + ": piece " + std::to_string(stop) + " (replica " + std::to_string(stop % n_rep) + "): " + pieces[stop].msg);
+        uint64_t n = 0;
+        for (uint32_t i = 0; i < n_pieces && i <= stop; ++i) n += pieces[i].n;
+        if (n >= (1ull << 32)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": more than 2^32 - 1 records");
+        std::string().swap(text);
+        const uint32_t n_nodes = (uint32_t)t->rows.size();
+        std::vector<cls_tally_row> rows(n_nodes, cls_tally_row{}), part(n_nodes);
+        cls_tally_totals totals{}, ptot{};
+        for (uint32_t r = 0; r < n_rep; ++r) {
+            if ((rc = cls_tally_read(tallies.v[r], part.data(), n_nodes, &ptot)) != CLS_OK) return fail(rc, cls_last_error());
+            if ((rc = cls_tally_merge(rows.data(), &totals, part.data(), &ptot, n_nodes)) != CLS_OK) return fail(rc, cls_last_error());
+        }
+        if ((rc = check_report_rows(who, t, rows.data())) != CLS_OK) return rc;
+        if ((rc = write_report(t, rows.data(), &totals, all_rows, report_path)) != CLS_OK) return rc;
+        if (n_placed) *n_placed = (uint32_t)n;
+        if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return CLS_OK;
+    } catch (const std::exception& ex) {
+        return fail(CLS_E_INTERNAL, std::string(who) + ": " + ex.what());
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, std::string(who) + ": unknown exception");
+    }
+}
+
+extern "C" int cls_profile_sequences(cls_db* db, const cls_tree* t, const char* query_path, const char* report_path,
+                                     const cls_params* params, int overwrite, int query_format, const cls_fastq_opts* fastq,
+                                     uint64_t piece_bytes, int all_rows, uint32_t* n_placed, double* seconds) {
+    if (!db || !t || !query_path || !report_path) return fail(CLS_E_INVALID_ARG, "cls_profile_sequences: null argument");
+    return profile_with("cls_profile_sequences", {db}, t, query_path, report_path, params, overwrite, query_format, fastq, piece_bytes, all_rows,
+                        n_placed, seconds);
+}
+
+extern "C" int cls_profile_sequences_group(cls_db_group* grp, const cls_tree* t, const char* query_path, const char* report_path,
+                                           const cls_params* params, int overwrite, int query_format, const cls_fastq_opts* fastq,
+                                           uint64_t piece_bytes, int all_rows, uint32_t* n_placed, double* seconds) {
+    if (!grp || !t || !query_path || !report_path) return fail(CLS_E_INVALID_ARG, "cls_profile_sequences_group: null argument");
+    uint32_t n_rep = 0;
+    int rc = cls_db_group_size(grp, &n_rep);
+    if (rc != CLS_OK) return fail(rc, cls_last_error());
+    try {
+        std::vector<cls_db*> dbs(n_rep, nullptr);
+        for (uint32_t i = 0; i < n_rep; ++i)
+            if ((rc = cls_db_group_replica(grp, i, &dbs[i])) != CLS_OK) return fail(rc, cls_last_error());
+        return profile_with("cls_profile_sequences_group", dbs, t, query_path, report_path, params, overwrite, query_format, fastq, piece_bytes,
+                            all_rows, n_placed, seconds);
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_profile_sequences_group: unknown exception");
+    }
 }

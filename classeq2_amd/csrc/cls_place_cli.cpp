@@ -2,6 +2,9 @@
 // (ports/cli/src/cmds/place_sequences.rs:18-82 flag surface, :84-223 behaviour) on the GPU path.
 //   cls-place [QUERY|-] -d DB -o OUT [-a ANNOTATIONS.yaml] [--out-format yaml|jsonl]
 //             [-i N] [-m COV] [-r] [-f] [--device N[,N...]] [--query-format fasta|fastq] [-q [5P,]3P]
+//             [--report PATH | --report-only PATH] [--report-all-clades]
+// --report also writes the per-clade abundance profile of the run (include/cls_host.h "clade report"); --report-only
+// writes nothing else: the reads are tallied on the device and no per-read output exists (-o is then not needed).
 // The database is read like load_database does (ports/lib/src/functions/load_database.rs:9-53): the `.cls`
 // file of `cls build-db` (zstd-compressed YAML), plain YAML, or the JSON export.
 #include <stdio.h>
@@ -30,7 +33,12 @@ static void usage() {
             "                                      index per entry (repeats allowed)\n"
             "      --query-format <fasta|fastq>    format of QUERY [default: fasta]; fastq = strict four-line FASTQ, Phred+33\n"
             "  -q, --trim-quality <[5P,]3P>        fastq only: trim low-quality ends (BWA / cutadapt -q rule); one value\n"
-            "                                      trims the 3' end, two values the 5' and the 3' end [default: 0,0 = off]\n");
+            "                                      trims the 3' end, two values the 5' and the 3' end [default: 0,0 = off]\n"
+            "      --report <PATH>                 also write the clade report: reads per clade (exactly at it / at or below\n"
+            "                                      it), per status, unplaced reads by reason (tab-separated text)\n"
+            "      --report-only <PATH>            write only the clade report: the reads are counted on the GPU, no per-read\n"
+            "                                      result or .error file is written and -o is not required\n"
+            "      --report-all-clades             list every clade in the report, not only those with reads\n");
 }
 
 // cutadapt's -q: "3P" or "5P,3P", each a cutoff in 0 .. 2^31 - 1
@@ -53,7 +61,8 @@ int main(int argc, char** argv) {
     memset(&p, 0, sizeof p);
     int overwrite = 0, device = 0;
     std::vector<int> devices;  // --device with a comma: an index group, one replica per entry
-    std::string qfmt = "fasta", trim;
+    std::string qfmt = "fasta", trim, report, report_only;
+    int all_rows = 0;
     cls_fastq_opts fq;
     memset(&fq, 0, sizeof fq);
     for (int i = 1; i < argc; ++i) {
@@ -89,10 +98,14 @@ int main(int argc, char** argv) {
         }
         else if (a == "--query-format") qfmt = need("--query-format");
         else if (a == "-q" || a == "--trim-quality") trim = need("--trim-quality");
+        else if (a == "--report") report = need("--report");
+        else if (a == "--report-only") report_only = need("--report-only");
+        else if (a == "--report-all-clades") all_rows = 1;
         else if (!a.empty() && a[0] == '-' && a != "-") { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); usage(); return 2; }
         else query = a;
     }
-    if (db_path.empty() || out_path.empty()) { usage(); return 2; }
+    if (db_path.empty() || (out_path.empty() && report_only.empty())) { usage(); return 2; }
+    if (!report.empty() && !report_only.empty()) { fprintf(stderr, "error: '--report' cannot be used with '--report-only'\n"); return 2; }
     if (fmt != "yaml" && fmt != "jsonl") { fprintf(stderr, "error: invalid value '%s' for '--out-format'\n", fmt.c_str()); return 2; }
     if (qfmt != "fasta" && qfmt != "fastq") { fprintf(stderr, "error: invalid value '%s' for '--query-format'\n", qfmt.c_str()); return 2; }
     if (!trim.empty()) {
@@ -120,7 +133,16 @@ int main(int argc, char** argv) {
     uint32_t n = 0;
     double seconds = 0;
     const int format = fmt == "yaml" ? CLS_FORMAT_YAML : CLS_FORMAT_JSONL;
-    int rc = db ? cls_place_sequences_ex(db, tree, query.c_str(), out_path.c_str(), &p, overwrite, format, query_format, &fq, &n, &seconds)
+    int rc;
+    if (!report_only.empty())
+        rc = db ? cls_profile_sequences(db, tree, query.c_str(), report_only.c_str(), &p, overwrite, query_format, &fq, 0, all_rows, &n, &seconds)
+                : cls_profile_sequences_group(group, tree, query.c_str(), report_only.c_str(), &p, overwrite, query_format, &fq, 0, all_rows, &n,
+                                              &seconds);
+    else if (!report.empty())
+        rc = cls_place_sequences_report(db, group, tree, query.c_str(), out_path.c_str(), &p, overwrite, format, query_format, &fq, report.c_str(),
+                                        all_rows, &n, &seconds);
+    else
+        rc = db ? cls_place_sequences_ex(db, tree, query.c_str(), out_path.c_str(), &p, overwrite, format, query_format, &fq, &n, &seconds)
                 : cls_place_sequences_group_ex(group, tree, query.c_str(), out_path.c_str(), &p, overwrite, format, query_format, &fq, &n,
                                                &seconds);
     if (rc != CLS_OK) fprintf(stderr, "%s\n", cls_host_last_error());

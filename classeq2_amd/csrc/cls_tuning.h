@@ -32,6 +32,7 @@ struct Tuning {
     int profile_stop = 0;         // CLS_PROFILE_STOP (needs a -DCLS_PROFILE_HOOKS build)
     int timing = 0;               // CLS_TIMING: phase times of cls_place_sequences on stderr
     int build_full_key = 0;       // CLS_BUILD_FULL_KEY: cls_kmers_build sorts the windows by (bucket key, hash) even without a 64-bit hash collision
+    int tally_no_wave_combine = 0; // CLS_TALLY_NO_WAVE_COMBINE: the tally kernel without its wave-level step (every record goes to the LDS table)
 };
 
 Tuning& tuning();

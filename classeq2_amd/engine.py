@@ -28,12 +28,14 @@ EXPORTS = [
     "cls_place_batch_device", "cls_place_batch_stats", "cls_fasta_parse", "cls_fasta_free", "cls_fasta_scan_device", "cls_fasta_dev_free",
     "cls_fasta_parse_gpu", "cls_place_fasta_text", "cls_fastq_parse", "cls_fastq_split", "cls_fastq_scan_device", "cls_fastq_parse_gpu",
     "cls_place_fastq_text", "cls_last_error",
+    "cls_tally_create", "cls_tally_destroy", "cls_tally_reset", "cls_tally_add_device", "cls_tally_add", "cls_tally_read", "cls_tally_host",
+    "cls_tally_merge", "cls_tally_fasta_text", "cls_tally_fastq_text",
     "cls_version", "cls_set_tuning", "cls_tuning_from_env", "cls_kmers_build", "cls_kmers_desc", "cls_kmers_info_get", "cls_kmers_free",
 ]
 HOST_EXPORTS = [
     "cls_tree_load_json", "cls_tree_load", "cls_tree_init_from_file", "cls_tree_from_newick", "cls_tree_serialize", "cls_tree_save", "cls_tree_free", "cls_tree_set_annotations_yaml", "cls_tree_build_kmers_map", "cls_tree_build_kmers_map_device", "cls_tree_desc", "cls_serialize_results",
     "cls_host_free", "cls_place_sequences", "cls_place_sequences_group", "cls_place_sequences_ex", "cls_place_sequences_group_ex",
-    "cls_host_last_error",
+    "cls_host_last_error", "cls_tally_report", "cls_profile_sequences", "cls_profile_sequences_group", "cls_place_sequences_report", "cls_tree_nodes",
 ]
 SERVICE_EXPORTS = [
     "cls_service_create", "cls_service_destroy", "cls_service_add_model", "cls_service_submit", "cls_service_wait", "cls_service_pause",
@@ -110,6 +112,27 @@ def lib():
         L.cls_place_fastq_text.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params), C.POINTER(_abi.FastqOpts), C.POINTER(_abi.Fasta),
                                            C.POINTER(vp)]
         L.cls_place_fastq_text.restype = i32
+        L.cls_tally_create.argtypes = [vp, C.POINTER(vp)]
+        L.cls_tally_create.restype = i32
+        L.cls_tally_destroy.argtypes = [vp]
+        L.cls_tally_destroy.restype = None
+        L.cls_tally_reset.argtypes = [vp]
+        L.cls_tally_reset.restype = i32
+        L.cls_tally_add_device.argtypes = [vp, vp, u32, vp]
+        L.cls_tally_add_device.restype = i32
+        L.cls_tally_add.argtypes = [vp, vp, u32]
+        L.cls_tally_add.restype = i32
+        L.cls_tally_read.argtypes = [vp, vp, u32, vp]
+        L.cls_tally_read.restype = i32
+        L.cls_tally_host.argtypes = [vp, u32, vp, C.c_uint64, vp, vp]
+        L.cls_tally_host.restype = i32
+        L.cls_tally_merge.argtypes = [vp, vp, vp, vp, u32]
+        L.cls_tally_merge.restype = i32
+        L.cls_tally_fasta_text.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params), C.POINTER(u32), C.POINTER(u32)]
+        L.cls_tally_fasta_text.restype = i32
+        L.cls_tally_fastq_text.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params), C.POINTER(_abi.FastqOpts), C.POINTER(u32),
+                                           C.POINTER(u32)]
+        L.cls_tally_fastq_text.restype = i32
         L.cls_fasta_free.argtypes = [C.POINTER(_abi.Fasta)]
         L.cls_fasta_free.restype = None
         L.cls_last_error.restype = C.c_char_p
@@ -165,6 +188,17 @@ def lib():
                                          C.POINTER(u32), C.POINTER(C.c_double)]
             getattr(L, name).restype = i32
         L.cls_host_last_error.restype = C.c_char_p
+        L.cls_tree_nodes.argtypes = [vp, C.POINTER(C.POINTER(_abi.Node)), C.POINTER(u32)]
+        L.cls_tree_nodes.restype = i32
+        L.cls_tally_report.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.cls_tally_report.restype = i32
+        for name in ("cls_profile_sequences", "cls_profile_sequences_group"):
+            getattr(L, name).argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.POINTER(_abi.Params), i32, i32, C.POINTER(_abi.FastqOpts), C.c_uint64, i32,
+                                         C.POINTER(u32), C.POINTER(C.c_double)]
+            getattr(L, name).restype = i32
+        L.cls_place_sequences_report.argtypes = [vp, vp, vp, C.c_char_p, C.c_char_p, C.POINTER(_abi.Params), i32, i32, i32, C.POINTER(_abi.FastqOpts),
+                                                 C.c_char_p, i32, C.POINTER(u32), C.POINTER(C.c_double)]
+        L.cls_place_sequences_report.restype = i32
         # resident batching service (include/cls_service.h)
         L.cls_service_create.argtypes = [C.POINTER(vp)]
         L.cls_service_create.restype = i32
@@ -434,6 +468,22 @@ class PlacementDb:
             lib().cls_fasta_free(C.byref(f))
             lib().cls_host_free(recs)
 
+    def tally_fasta_text(self, tally: "Tally", text: bytes, params: Optional[_abi.Params] = None):
+        """FASTA text -> records added to `tally` on the device; nothing per read returns (cls_tally_fasta_text)
+        -> (records placed, truncated)."""
+        n, tr = C.c_uint32(0), C.c_uint32(0)
+        pp = C.byref(params) if params is not None else None
+        _check(lib().cls_tally_fasta_text(self._h, tally._h, text, len(text), pp, C.byref(n), C.byref(tr)))
+        return n.value, bool(tr.value)
+
+    def tally_fastq_text(self, tally: "Tally", text: bytes, params: Optional[_abi.Params] = None, trim_5p: int = 0, trim_3p: int = 0):
+        """The FASTQ twin (cls_tally_fastq_text) -> (records placed, truncated)."""
+        n, tr = C.c_uint32(0), C.c_uint32(0)
+        pp = C.byref(params) if params is not None else None
+        o = _fastq_opts(trim_5p, trim_3p)
+        _check(lib().cls_tally_fastq_text(self._h, tally._h, text, len(text), pp, C.byref(o), C.byref(n), C.byref(tr)))
+        return n.value, bool(tr.value)
+
     def set_max_read_len(self, n_bases: int) -> None:
         """Longest read place_batch_device() provisions for (cls_db_set_max_read_len)."""
         _check(lib().cls_db_set_max_read_len(self._h, n_bases))
@@ -444,6 +494,77 @@ class PlacementDb:
         """Device pointers in/out, asynchronous on `stream` (cls_place_batch_device)."""
         pp = C.byref(params) if params is not None else None
         _check(lib().cls_place_batch_device(self._h, d_bases, d_offsets, n, pp, d_out, d_stats or None, stream or None))
+
+
+class Tally:
+    """Device-resident per-clade accumulator bound to one PlacementDb (cls_tally): add placement records batch after
+    batch, read one row per clade (in the row order of the FlatDb the handle was made from) plus totals."""
+
+    def __init__(self, db: PlacementDb):
+        self._db = db  # (the tally borrows the handle)
+        self._h = C.c_void_p()
+        _check(lib().cls_tally_create(db._h, C.byref(self._h)))
+        self.n_nodes = int(db.info.n_nodes)
+
+    def add(self, records: np.ndarray) -> None:
+        """Host records: copied to the device and added there (cls_tally_add)."""
+        recs = np.ascontiguousarray(records, dtype=_abi.PLACEMENT_DTYPE)
+        _check(lib().cls_tally_add(self._h, recs.ctypes.data, len(recs)))
+
+    def add_device(self, d_records: int, n: int, stream: int = 0) -> None:
+        """`n` records in the HBM of the handle's device, asynchronous on `stream` (cls_tally_add_device)."""
+        _check(lib().cls_tally_add_device(self._h, d_records or None, n, stream or None))
+
+    def read(self):
+        """-> (rows TALLY_ROW_DTYPE[n_nodes], totals: TALLY_TOTALS_DTYPE scalar); waits for the adds in flight."""
+        rows = np.zeros(self.n_nodes, dtype=_abi.TALLY_ROW_DTYPE)
+        totals = np.zeros(1, dtype=_abi.TALLY_TOTALS_DTYPE)
+        _check(lib().cls_tally_read(self._h, rows.ctypes.data, len(rows), totals.ctypes.data))
+        return rows, totals[0]
+
+    def reset(self) -> None:
+        _check(lib().cls_tally_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().cls_tally_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def tally_host(flat: FlatDb, records: np.ndarray, rows: Optional[np.ndarray] = None, totals: Optional[np.ndarray] = None):
+    """The counting rules of the clade tally on the host, no device (cls_tally_host) -> (rows, totals) in the row order
+    of `flat.nodes`.  `rows` / `totals` (a 1-element TALLY_TOTALS_DTYPE array) from an earlier call are added to in place."""
+    nodes = np.ascontiguousarray(flat.nodes, dtype=_abi.NODE_DTYPE)
+    recs = np.ascontiguousarray(records, dtype=_abi.PLACEMENT_DTYPE)
+    if rows is None:
+        rows = np.zeros(len(nodes), dtype=_abi.TALLY_ROW_DTYPE)
+    if totals is None:
+        totals = np.zeros(1, dtype=_abi.TALLY_TOTALS_DTYPE)
+    assert rows.dtype == _abi.TALLY_ROW_DTYPE and len(rows) == len(nodes) and rows.flags.c_contiguous
+    assert totals.dtype == _abi.TALLY_TOTALS_DTYPE and totals.shape == (1,)
+    _check(lib().cls_tally_host(nodes.ctypes.data, len(nodes), recs.ctypes.data, len(recs), rows.ctypes.data, totals.ctypes.data))
+    return rows, totals
+
+
+def tally_merge(rows: np.ndarray, totals: np.ndarray, add_rows: np.ndarray, add_totals) -> None:
+    """rows += add_rows, totals += add_totals in place (cls_tally_merge): how the tallies of replicas or ranks are summed."""
+    add_rows = np.ascontiguousarray(add_rows, dtype=_abi.TALLY_ROW_DTYPE)
+    add_totals = np.ascontiguousarray(np.atleast_1d(add_totals), dtype=_abi.TALLY_TOTALS_DTYPE)
+    assert rows.dtype == _abi.TALLY_ROW_DTYPE and len(rows) == len(add_rows) and rows.flags.c_contiguous
+    assert totals.dtype == _abi.TALLY_TOTALS_DTYPE and totals.shape == (1,)
+    _check(lib().cls_tally_merge(rows.ctypes.data, totals.ctypes.data, add_rows.ctypes.data, add_totals.ctypes.data, len(rows)))
 
 
 class _ReplicaView(PlacementDb):
@@ -587,6 +708,27 @@ class Tree:
         _check_host(lib().cls_tree_desc(self._h, C.byref(d)))
         return FlatDb.from_desc(d, keepalive=self)
 
+    def nodes(self) -> np.ndarray:
+        """The tree's node table (NODE_DTYPE rows, a copy), also for a tree-only file (cls_tree_nodes)."""
+        p, n = C.POINTER(_abi.Node)(), C.c_uint32(0)
+        _check_host(lib().cls_tree_nodes(self._h, C.byref(p), C.byref(n)))
+        return np.frombuffer(C.string_at(p, n.value * 32), dtype=_abi.NODE_DTYPE).copy()
+
+    def report(self, rows: np.ndarray, totals, all_rows: bool = False) -> bytes:
+        """The clade report (cls_tally_report, format in include/cls_host.h) of a tally over this tree: `rows` in the
+        row order of flat().nodes, as Tally.read / tally_host return them."""
+        rows = np.ascontiguousarray(rows, dtype=_abi.TALLY_ROW_DTYPE)
+        tot = np.ascontiguousarray(np.atleast_1d(totals), dtype=_abi.TALLY_TOTALS_DTYPE)
+        n_nodes = len(self.nodes())
+        if len(rows) != n_nodes:
+            raise ValueError(f"{len(rows)} rows for a tree of {n_nodes} clades")
+        buf, n = C.c_void_p(), C.c_size_t()
+        _check_host(lib().cls_tally_report(self._h, rows.ctypes.data, tot.ctypes.data, 1 if all_rows else 0, C.byref(buf), C.byref(n)))
+        try:
+            return C.string_at(buf, n.value)
+        finally:
+            lib().cls_host_free(buf)
+
     def serialize(self, headers, records: np.ndarray, fmt: int = FORMAT_YAML):
         """-> (result text, error text) exactly as `place_sequences` would append them to its two files."""
         hb = [h if isinstance(h, bytes) else h.encode() for h in headers]
@@ -601,6 +743,32 @@ class Tree:
         finally:
             lib().cls_host_free(out)
             lib().cls_host_free(err)
+
+
+def _trim_pair(trim_quality):
+    if trim_quality is None:
+        return 0, 0
+    if isinstance(trim_quality, int):
+        return 0, trim_quality
+    return trim_quality
+
+
+def profile_sequences(db, tree: Tree, query_path: str, report_path: str, params: Optional[_abi.Params] = None, overwrite: bool = False,
+                      query_format: str = "fasta", trim_quality=None, piece_bytes: int = 0, all_rows: bool = False):
+    """Query file -> clade report with the reads tallied on the device (cls_profile_sequences, or
+    cls_profile_sequences_group when `db` is a PlacementDbGroup) -> (records tallied, seconds).  `piece_bytes`: the
+    query is processed in pieces of about that size (0: the library's default)."""
+    if query_format not in ("fasta", "fastq"):
+        raise ValueError(f"query_format must be 'fasta' or 'fastq', not {query_format!r}")
+    if trim_quality is not None and query_format != "fastq":
+        raise ValueError("trim_quality needs query_format='fastq'")
+    n, sec = C.c_uint32(0), C.c_double(0)
+    o = _fastq_opts(*_trim_pair(trim_quality))
+    fn = lib().cls_profile_sequences_group if isinstance(db, PlacementDbGroup) else lib().cls_profile_sequences
+    _check_host(fn(db._h, tree._h, query_path.encode(), report_path.encode(), C.byref(params) if params is not None else None,
+                   1 if overwrite else 0, _abi.QUERY_FASTQ if query_format == "fastq" else _abi.QUERY_FASTA, C.byref(o), piece_bytes,
+                   1 if all_rows else 0, C.byref(n), C.byref(sec)))
+    return n.value, sec.value
 
 
 def place_sequences(db, tree: Tree, query_path: str, out_file: str, params: Optional[_abi.Params] = None,

@@ -97,6 +97,46 @@ int cls_place_sequences_group_ex(cls_db_group* g, const cls_tree* t, const char*
                                  const cls_params* params, int overwrite, int format, int query_format,
                                  const cls_fastq_opts* fastq, uint32_t* n_placed, double* seconds);
 
+/* Borrowed node table of the tree (the `nodes` of cls_tree_desc), also for a tree-only file; valid while `t` lives. */
+int cls_tree_nodes(const cls_tree* t, const cls_node** nodes, uint32_t* n_nodes);
+
+/* ---- clade report: the per-clade abundance profile of a run (the clade tally of cls_place.h as a text file) ------
+ * `rows` = one cls_tally_row per row of the tree's node table (cls_tree_desc order: what cls_tally_read and
+ * cls_tally_host give for it), `totals` with them.  Tab-separated text, "\n" line ends (release with cls_host_free):
+ *   # classeq2_amd clade report v1
+ *   # reads\t<n_reads>
+ *   # status\t<NAME>\t<count>            twelve lines, in enum order (UNCLASSIFIABLE_NO_MATCH .. ERR_READ_TOO_LONG)
+ *   # unknown_clade\t<n>
+ *   # bad_status\t<n>
+ *   clade_id\tparent_id\tkind\tdepth\tname\tn_clade\tn_direct\tn_identity\tn_max_resolution\tn_inconclusive\tmean_one\tmean_rest
+ *   one line per clade in DFS pre-order (children in Clade.children order); without `all_rows` only the clades with
+ *   n_clade > 0.  parent_id: "-" for the root; kind: ROOT / NODE / LEAF; depth: levels below the root; name: the
+ *   clade's name or empty; mean_one / mean_rest: sum / n_identity with "%.3f", or "-" when n_identity is 0. */
+int cls_tally_report(const cls_tree* t, const cls_tally_row* rows, const cls_tally_totals* totals, int all_rows,
+                     char** out_text, size_t* out_len);
+/* Query file -> clade report, nothing per read leaves the device: the query (`query_path`, "-" = stdin) is cut with
+ * cls_fasta_split / cls_fastq_split into pieces of about `piece_bytes` (0: 64 MiB), each piece goes through
+ * cls_tally_fasta_text / cls_tally_fastq_text into ONE tally (device memory is bounded by the piece, not by the file),
+ * the pieces after the first one that stops early (`truncated`) are dropped as cls_place_sequences_group drops them,
+ * and the report is written to `report_path` (no extension is forced; an existing file needs `overwrite`).
+ * `n_placed`: records tallied.  `seconds`: read + place + write.  query_format / fastq as cls_place_sequences_ex. */
+int cls_profile_sequences(cls_db* db, const cls_tree* t, const char* query_path, const char* report_path,
+                          const cls_params* params, int overwrite, int query_format, const cls_fastq_opts* fastq,
+                          uint64_t piece_bytes, int all_rows, uint32_t* n_placed, double* seconds);
+/* The same on an index group: piece i goes to replica i mod N, every replica on a host thread of its own with a tally
+ * of its own; the replicas' rows and totals are summed with cls_tally_merge.  The report is byte-identical to the
+ * one of cls_profile_sequences. */
+int cls_profile_sequences_group(cls_db_group* g, const cls_tree* t, const char* query_path, const char* report_path,
+                                const cls_params* params, int overwrite, int query_format, const cls_fastq_opts* fastq,
+                                uint64_t piece_bytes, int all_rows, uint32_t* n_placed, double* seconds);
+/* cls_place_sequences_ex / cls_place_sequences_group_ex (exactly one of `db`, `g` is non-NULL) that also write the
+ * clade report of the run to `report_path`, counted on the host (cls_tally_host) from the records the run has anyway:
+ * no second placement.  The report is byte-identical to the one cls_profile_sequences writes for the same input. */
+int cls_place_sequences_report(cls_db* db, cls_db_group* g, const cls_tree* t, const char* query_path, const char* out_file,
+                               const cls_params* params, int overwrite, int format, int query_format,
+                               const cls_fastq_opts* fastq, const char* report_path, int all_rows, uint32_t* n_placed,
+                               double* seconds);
+
 const char* cls_host_last_error(void);
 
 #ifdef __cplusplus

@@ -434,6 +434,70 @@ int cls_fastq_parse_gpu(const char* text, size_t len, const cls_fastq_opts* opts
 int cls_place_fastq_text(cls_db* db, const char* text, size_t len, const cls_params* params, const cls_fastq_opts* opts,
                          cls_fasta* fa, cls_placement** records);
 
+/* ---- clade tally: placement records -> a per-clade abundance profile -------------
+ * A tally is a small accumulator in the HBM of one handle's device.  Records are added to it batch after batch;
+ * reading it gives one row per clade plus totals.  The counting rules, for a set of records and the tree of a handle:
+ *   - status_count[s], s = 0 .. 11: records with that status.  n_reads: all records added.
+ *   - a record is CLADE-BEARING iff its status is CLS_IDENTITY_FOUND, CLS_MAX_RESOLUTION or CLS_INCONCLUSIVE (the
+ *     outcomes for which `clade_id` is set); for every other status `clade_id` is not looked at.
+ *   - per clade v: n_identity, n_max_resolution, n_inconclusive = clade-bearing records with clade_id == id(v), by
+ *     status; n_direct = their sum; n_clade = the sum of n_direct over v and every descendant of v; sum_one, sum_rest
+ *     = the sums of `one` and `rest` over the CLS_IDENTITY_FOUND records of v only, as signed 64-bit sums.
+ *   - a clade-bearing record whose clade_id is no clade of the tree counts in n_unknown_clade and in its
+ *     status_count, in no row.  A record with status >= 12 counts in n_bad_status and in n_reads, nowhere else.
+ *     Neither is an error: the entries take whatever bytes the caller's buffer holds (padding bytes are ignored).
+ *   - every counter is 64 bits wide and everything is integer: adding is associative and commutative, the tally after
+ *     adding batches A then B is the tally of their concatenation, in any order and any split, exactly.
+ *   - rows come back in the row order of the cls_db_desc.nodes the handle was created from: row i describes nodes[i]
+ *     and carries its id. */
+typedef struct cls_tally cls_tally;   /* opaque; bound to one cls_db, lives on its device */
+typedef struct cls_tally_row {
+    uint64_t id;
+    uint64_t n_clade;
+    uint64_t n_direct;
+    uint64_t n_identity;
+    uint64_t n_max_resolution;
+    uint64_t n_inconclusive;
+    int64_t sum_one;
+    int64_t sum_rest;
+} cls_tally_row;                      /* 64 bytes */
+typedef struct cls_tally_totals {
+    uint64_t n_reads;
+    uint64_t status_count[12];
+    uint64_t n_unknown_clade;
+    uint64_t n_bad_status;
+} cls_tally_totals;                   /* 120 bytes */
+
+/* A zeroed tally on the device of `db`.  It borrows the handle (a replica of a group included): destroy it first. */
+int cls_tally_create(cls_db* db, cls_tally** out);
+void cls_tally_destroy(cls_tally* t);
+/* Waits for the adds in flight, then zeroes every counter. */
+int cls_tally_reset(cls_tally* t);
+/* `n` records already in the HBM of the handle's device (the d_out of cls_place_batch_device), 8-byte aligned;
+ * asynchronous on `hip_stream`, in stream order behind whatever wrote them.  Adds on different streams may overlap. */
+int cls_tally_add_device(cls_tally* t, const void* d_records, uint32_t n, void* hip_stream);
+/* Host records: copied to the device and added by the same kernel; synchronous. */
+int cls_tally_add(cls_tally* t, const cls_placement* records, uint32_t n);
+/* Waits for the adds in flight; the subtree sums are made on the device.  `rows` holds n_rows = the tree's n_nodes
+ * entries; `rows` (with n_rows = 0) or `totals` may be NULL. */
+int cls_tally_read(cls_tally* t, cls_tally_row* rows, uint32_t n_rows, cls_tally_totals* totals);
+/* Host only, sequential, no device: the statement of the rules above and the yardstick of the kernel.  Takes the tree
+ * as cls_db_create takes it.  rows[n_nodes] and `totals` are ADDED to (the caller zeroes them before the first call;
+ * row ids are set), so the call also merges: the tallies of the replicas of an index group are summed by adding
+ * each one's rows and totals (see cls_tally_merge). */
+int cls_tally_host(const cls_node* nodes, uint32_t n_nodes, const cls_placement* records, uint64_t n,
+                   cls_tally_row* rows, cls_tally_totals* totals);
+/* rows[i] += add_rows[i] for n_rows rows (ids must agree, or the target's are 0 and are set), totals += add_totals. */
+int cls_tally_merge(cls_tally_row* rows, cls_tally_totals* totals, const cls_tally_row* add_rows,
+                    const cls_tally_totals* add_totals, uint32_t n_rows);
+/* Query text -> tally; nothing per read returns to the host: H2D of the text, the device FASTA / FASTQ stage,
+ * placement, cls_tally_add_device on its output.  *n = records placed, *truncated as cls_fasta.truncated (either
+ * may be NULL).  Synchronous. */
+int cls_tally_fasta_text(cls_db* db, cls_tally* t, const char* text, size_t len, const cls_params* params,
+                         uint32_t* n, uint32_t* truncated);
+int cls_tally_fastq_text(cls_db* db, cls_tally* t, const char* text, size_t len, const cls_params* params,
+                         const cls_fastq_opts* opts, uint32_t* n, uint32_t* truncated);
+
 /* Experiment knobs (grid sizes, locality-key definition, kernel family; none changes a result; names in
  * csrc/cls_tuning.h are the CLS_* variables in lower case without the prefix, e.g. "no_order").  Process-global,
  * meant for A/B runs: the library itself never reads the environment.  cls_tuning_from_env() takes every knob
