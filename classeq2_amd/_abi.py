@@ -260,5 +260,12 @@ TALLY_ROW_DTYPE = np.dtype(
      ("sum_one", "<i8"), ("sum_rest", "<i8")]
 )
 TALLY_TOTALS_DTYPE = np.dtype([("n_reads", "<u8"), ("status_count", "<u8", (12,)), ("n_unknown_clade", "<u8"), ("n_bad_status", "<u8")])
+# paired reads (cls_pair_totals, CLS_PAIR_*)
+(PAIR_NEITHER, PAIR_ONLY_1, PAIR_ONLY_2, PAIR_SAME, PAIR_NESTED_1, PAIR_NESTED_2, PAIR_DISCORDANT) = range(7)
+PAIR_CLASS_NAMES = ["NEITHER", "ONLY_1", "ONLY_2", "SAME", "NESTED_1", "NESTED_2", "DISCORDANT"]
+PAIR_CONSERVATIVE, PAIR_REQUIRE_BOTH = 1, 2
+E_BAD_PAIRS = -8
+PAIR_TOTALS_DTYPE = np.dtype([("n_pairs", "<u8"), ("how_count", "<u8", (8,))])
+assert PAIR_TOTALS_DTYPE.itemsize == 72
 assert NODE_DTYPE.itemsize == 32 and PLACEMENT_DTYPE.itemsize == 24 and STATS_DTYPE.itemsize == 24
 assert TALLY_ROW_DTYPE.itemsize == 64 and TALLY_TOTALS_DTYPE.itemsize == 120

@@ -17,6 +17,7 @@
 #include "cls_db.h"
 #include "cls_device.h"
 #include "cls_kernels.h"
+#include "cls_pair.h"
 #include "cls_place.h"
 #include "cls_tally.h"
 #include "cls_tuning.h"
@@ -1319,6 +1320,537 @@ extern "C" int cls_tally_fastq_text(cls_db* db, cls_tally* t, const char* text, 
                               opts, &fa, nullptr, t);
     if (rc != CLS_OK) return rc;
     if (n) *n = fa.n;
+    if (truncated) *truncated = fa.truncated;
+    return CLS_OK;
+}
+
+// ---- paired reads (include/cls_place.h; kernels in cls_pair.hip) ----------------------------------------------------
+
+struct cls_pairer {
+    cls_db* db = nullptr;
+    cls::PairDev dev{};
+    void* d_table = nullptr;      // a copy of the tally's id table: the tally's own objects stay as they are
+    void* d_tree = nullptr;       // size_by_pre[n] | parent_by_pre[n] | depth_by_pre[n]
+    void* d_id = nullptr;         // id_by_pre[n]
+    void* d_totals = nullptr;     // PAIR_CLASSES counters
+    hipStream_t stream = nullptr; // read-out, reset and the host-record calls
+    std::mutex mu;
+    struct Mark { hipStream_t stream; hipEvent_t ev; };
+    std::vector<Mark> marks;      // per caller stream: an event behind its last launch (cls_pairer_totals waits for them)
+};
+constexpr size_t MAX_PAIR_MARKS = 64;
+
+extern "C" void cls_pairer_destroy(cls_pairer* p) {
+    if (!p) return;
+    DeviceScope ds;
+    (void)ds.enter(p->db->device);
+    for (auto& m : p->marks) { (void)hipEventSynchronize(m.ev); (void)hipEventDestroy(m.ev); }
+    if (p->stream) { (void)hipStreamSynchronize(p->stream); (void)hipStreamDestroy(p->stream); }
+    for (void* x : {p->d_table, p->d_tree, p->d_id, p->d_totals}) if (x) (void)hipFree(x);
+    delete p;
+}
+
+extern "C" int cls_pairer_create(cls_db* db, cls_pairer** out) {
+    if (!db || !out) return fail(CLS_E_INVALID_ARG, "cls_pairer_create: null argument");
+    *out = nullptr;
+    cls_pairer* p = nullptr;
+    try {
+        const uint32_t n = (uint32_t)db->tree_rows.size();
+        if (n == 0 || n >= cls::TALLY_MAX_NODES) return fail(CLS_E_INVALID_ARG, "cls_pairer_create: the tree has too many clades for a pairer");
+        uint32_t cap = 16;
+        while (cap < 2 * n) cap *= 2;
+        std::vector<cls::IdSlot> table(cap, cls::IdSlot{0, cls::TALLY_NO_PRE, 0});
+        std::vector<uint32_t> tree(3 * (size_t)n);  // size | parent | depth, by pre
+        std::vector<uint64_t> id_by_pre(n);
+        uint32_t* size_by_pre = tree.data();
+        uint32_t* parent_by_pre = tree.data() + n;
+        uint32_t* depth_by_pre = tree.data() + 2 * (size_t)n;
+        for (const auto& r : db->tree_rows) {
+            uint32_t h = (uint32_t)cls::tally_hash(r.id) & (cap - 1);
+            while (table[h].pre != cls::TALLY_NO_PRE) h = (h + 1) & (cap - 1);
+            table[h].id = r.id;
+            table[h].pre = r.pre;
+            size_by_pre[r.pre] = r.size;
+            id_by_pre[r.pre] = r.id;
+        }
+        // parents and depths from the intervals: the clades open at pre-order index q are the ancestors of q
+        std::vector<uint32_t> open;
+        for (uint32_t q = 0; q < n; ++q) {
+            while (!open.empty() && (uint64_t)open.back() + size_by_pre[open.back()] <= q) open.pop_back();
+            parent_by_pre[q] = open.empty() ? q : open.back();
+            depth_by_pre[q] = (uint32_t)open.size();
+            open.push_back(q);
+        }
+        DeviceScope ds;
+        CLS_HIP(ds.enter(db->device));
+        p = new cls_pairer();
+        p->db = db;
+        hipError_t e;
+        if ((e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking)) != hipSuccess ||
+            (e = hipMalloc(&p->d_table, (size_t)cap * sizeof(cls::IdSlot))) != hipSuccess ||
+            (e = hipMalloc(&p->d_tree, tree.size() * 4)) != hipSuccess ||
+            (e = hipMalloc(&p->d_id, (size_t)n * 8)) != hipSuccess ||
+            (e = hipMalloc(&p->d_totals, cls::PAIR_CLASSES * 8)) != hipSuccess ||
+            (e = hipMemcpyAsync(p->d_table, table.data(), (size_t)cap * sizeof(cls::IdSlot), hipMemcpyHostToDevice, p->stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(p->d_tree, tree.data(), tree.size() * 4, hipMemcpyHostToDevice, p->stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(p->d_id, id_by_pre.data(), (size_t)n * 8, hipMemcpyHostToDevice, p->stream)) != hipSuccess ||
+            (e = hipMemsetAsync(p->d_totals, 0, cls::PAIR_CLASSES * 8, p->stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(p->stream)) != hipSuccess) {
+            cls_pairer_destroy(p);
+            return fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string("cls_pairer_create: ") + hipGetErrorString(e));
+        }
+        cls::PairDev& d = p->dev;
+        d.table = (const cls::IdSlot*)p->d_table;
+        d.table_mask = cap - 1;
+        d.n_nodes = n;
+        d.size_by_pre = (const uint32_t*)p->d_tree;
+        d.parent_by_pre = (const uint32_t*)p->d_tree + n;
+        d.depth_by_pre = (const uint32_t*)p->d_tree + 2 * (size_t)n;
+        d.id_by_pre = (const uint64_t*)p->d_id;
+        d.totals = (unsigned long long*)p->d_totals;
+        *out = p;
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        cls_pairer_destroy(p);
+        return fail(CLS_E_NOMEM, "cls_pairer_create: out of host memory");
+    } catch (...) {
+        cls_pairer_destroy(p);
+        return fail(CLS_E_INTERNAL, "cls_pairer_create: unknown exception");
+    }
+}
+
+extern "C" int cls_pairer_totals(cls_pairer* p, cls_pair_totals* totals, int reset) {
+    if (!p || !totals) return fail(CLS_E_INVALID_ARG, "cls_pairer_totals: null argument");
+    DeviceScope ds;
+    CLS_HIP(ds.enter(p->db->device));
+    std::lock_guard<std::mutex> g(p->mu);
+    for (auto& m : p->marks) CLS_HIP(hipEventSynchronize(m.ev));
+    unsigned long long tot[cls::PAIR_CLASSES];
+    CLS_HIP(hipMemcpyAsync(tot, p->d_totals, sizeof tot, hipMemcpyDeviceToHost, p->stream));
+    if (reset) CLS_HIP(hipMemsetAsync(p->d_totals, 0, sizeof tot, p->stream));
+    CLS_HIP(hipStreamSynchronize(p->stream));
+    memset(totals, 0, sizeof *totals);
+    for (int s = 0; s < 7; ++s) { totals->how_count[s] = tot[s]; totals->n_pairs += tot[s]; }
+    return CLS_OK;
+}
+
+static int check_pair_flags(const char* who, uint32_t stride, uint32_t flags) {
+    if (stride != 1 && stride != 2) return fail(CLS_E_INVALID_ARG, std::string(who) + ": stride must be 1 or 2");
+    if (flags & ~(CLS_PAIR_CONSERVATIVE | CLS_PAIR_REQUIRE_BOTH)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": unknown flag bit");
+    return CLS_OK;
+}
+
+// The launch on `stream` (the handle's device is current), and the mark cls_pairer_totals waits for.
+// `mark` = false: the caller synchronises `stream` itself before it returns.
+static int pair_on(cls_pairer* p, const void* d_a, const void* d_b, uint32_t stride, uint32_t n, uint32_t flags, void* d_out, void* d_how,
+                   hipStream_t stream, bool mark = true) {
+    const uintptr_t a = (uintptr_t)d_a, b = (uintptr_t)d_b, o = (uintptr_t)d_out;
+    const size_t rec = sizeof(cls_placement);
+    if ((a | b | o) & 7) return fail(CLS_E_INVALID_ARG, "cls_pair_records_device: records must be 8-byte aligned");
+    if (stride == 2 && b != a + rec) return fail(CLS_E_INVALID_ARG, "cls_pair_records_device: stride 2 takes d_b = d_a + one record");
+    auto overlaps = [&](uintptr_t x, uint64_t n_recs) { return o < x + n_recs * rec && x < o + (uint64_t)n * rec; };
+    if (overlaps(a, stride == 2 ? 2ull * n : n) || (stride == 1 && overlaps(b, n)))
+        return fail(CLS_E_INVALID_ARG, "cls_pair_records_device: d_out must not alias the inputs");
+    std::lock_guard<std::mutex> g(p->mu);
+    CLS_HIP(cls::launch_pair_records(p->dev, d_a, d_b, stride, n, flags, d_out, d_how, (uint32_t)p->db->n_cu, stream));
+    if (!mark) return CLS_OK;
+    // (hipStreamPerThread is one handle value that names a different stream in every host thread: never cached)
+    if (stream != hipStreamPerThread) {
+        for (auto& m : p->marks)
+            if (m.stream == stream) { CLS_HIP(hipEventRecord(m.ev, stream)); return CLS_OK; }
+        if (p->marks.size() < MAX_PAIR_MARKS) {
+            hipEvent_t ev = nullptr;
+            CLS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            if (hipEventRecord(ev, stream) != hipSuccess) { (void)hipEventDestroy(ev); return fail(CLS_E_HIP, "cls_pair_records_device: hipEventRecord failed"); }
+            p->marks.push_back({stream, ev});
+            return CLS_OK;
+        }
+    }
+    CLS_HIP(hipStreamSynchronize(stream));  // no mark to leave: the launch is waited for here
+    return CLS_OK;
+}
+
+extern "C" int cls_pair_records_device(cls_pairer* p, const void* d_a, const void* d_b, uint32_t stride, uint32_t n, uint32_t flags,
+                                       void* d_out, void* d_how, void* hip_stream) {
+    if (!p) return fail(CLS_E_INVALID_ARG, "cls_pair_records_device: null handle");
+    if (int rc = check_pair_flags("cls_pair_records_device", stride, flags)) return rc;
+    if (n == 0) return CLS_OK;
+    if (!d_a || !d_b || !d_out) return fail(CLS_E_INVALID_ARG, "cls_pair_records_device: null buffer");
+    DeviceScope ds;
+    CLS_HIP(ds.enter(p->db->device));
+    try {
+        return pair_on(p, d_a, d_b, stride, n, flags, d_out, d_how, (hipStream_t)hip_stream);
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_pair_records_device: unknown exception");
+    }
+}
+
+extern "C" int cls_pair_records(cls_pairer* p, const cls_placement* a, const cls_placement* b, uint32_t stride, uint32_t n, uint32_t flags,
+                                cls_placement* out, uint8_t* how) {
+    if (!p) return fail(CLS_E_INVALID_ARG, "cls_pair_records: null handle");
+    if (int rc = check_pair_flags("cls_pair_records", stride, flags)) return rc;
+    if (n == 0) return CLS_OK;
+    if (!a || !b || !out) return fail(CLS_E_INVALID_ARG, "cls_pair_records: null buffer");
+    if (stride == 2 && b != a + 1) return fail(CLS_E_INVALID_ARG, "cls_pair_records: stride 2 takes b = a + 1");
+    DeviceScope ds;
+    CLS_HIP(ds.enter(p->db->device));
+    const size_t rec = sizeof(cls_placement), in_recs = 2 * (size_t)n;
+    char* d = nullptr;  // mate 1 | mate 2 (or the interleaved records) | P | how
+    hipError_t e = hipMalloc((void**)&d, (in_recs + n) * rec + n);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string("cls_pair_records: ") + hipGetErrorString(e));
+    char *d_a = d, *d_b = stride == 2 ? d + rec : d + (size_t)n * rec, *d_out = d + in_recs * rec, *d_how = d_out + (size_t)n * rec;
+    int rc = CLS_OK;
+    try {
+        if (stride == 2) e = hipMemcpyAsync(d_a, a, in_recs * rec, hipMemcpyHostToDevice, p->stream);
+        else if ((e = hipMemcpyAsync(d_a, a, (size_t)n * rec, hipMemcpyHostToDevice, p->stream)) == hipSuccess)
+            e = hipMemcpyAsync(d_b, b, (size_t)n * rec, hipMemcpyHostToDevice, p->stream);
+        if (e != hipSuccess) rc = fail(CLS_E_HIP, std::string("cls_pair_records: ") + hipGetErrorString(e));
+        else rc = pair_on(p, d_a, d_b, stride, n, flags, d_out, d_how, p->stream, false);
+        if (rc == CLS_OK && ((e = hipMemcpyAsync(out, d_out, (size_t)n * rec, hipMemcpyDeviceToHost, p->stream)) != hipSuccess ||
+                             (how && (e = hipMemcpyAsync(how, d_how, n, hipMemcpyDeviceToHost, p->stream)) != hipSuccess)))
+            rc = fail(CLS_E_HIP, std::string("cls_pair_records: ") + hipGetErrorString(e));
+    } catch (...) {
+        rc = fail(CLS_E_INTERNAL, "cls_pair_records: unknown exception");
+    }
+    e = hipStreamSynchronize(p->stream);  // synchronous; the staging copy is freed behind the kernel
+    if (rc == CLS_OK && e != hipSuccess) rc = fail(CLS_E_HIP, std::string("cls_pair_records: ") + hipGetErrorString(e));
+    (void)hipFree(d);
+    return rc;
+}
+
+// The pairing rule as it is written in cls_place.h, one pair after the other: a sorted id -> row list, parent rows and
+// depths from the child ranges, the LCA by climbing from the deeper clade.
+extern "C" int cls_pair_host(const cls_node* nodes, uint32_t n_nodes, const cls_placement* a, const cls_placement* b, uint32_t stride,
+                             uint64_t n, uint32_t flags, cls_placement* out, uint8_t* how, cls_pair_totals* totals) {
+    if (!nodes || n_nodes == 0 || (n && (!a || !b || !out))) return fail(CLS_E_INVALID_ARG, "cls_pair_host: null argument");
+    if (int rc = check_pair_flags("cls_pair_host", stride, flags)) return rc;
+    try {
+        constexpr uint32_t NONE = UINT32_MAX;
+        std::vector<uint32_t> parent_row(n_nodes, NONE), depth(n_nodes, 0);
+        std::vector<std::pair<uint64_t, uint32_t>> by_id(n_nodes);
+        for (uint32_t r = 0; r < n_nodes; ++r) {
+            by_id[r] = {nodes[r].id, r};
+            if (nodes[r].n_children == 0) continue;
+            if ((uint64_t)nodes[r].first_child + nodes[r].n_children > n_nodes || nodes[r].first_child == 0)
+                return fail(CLS_E_BAD_TREE, "cls_pair_host: child rows out of range");
+            for (uint32_t c = nodes[r].first_child; c < nodes[r].first_child + nodes[r].n_children; ++c) {
+                if (parent_row[c] != NONE) return fail(CLS_E_BAD_TREE, "cls_pair_host: row is the child of two parents (not a tree)");
+                parent_row[c] = r;
+            }
+        }
+        if (parent_row[0] != NONE) return fail(CLS_E_BAD_TREE, "cls_pair_host: the root has a parent");
+        std::vector<uint32_t> bfs;  // parents before their children
+        bfs.reserve(n_nodes);
+        bfs.push_back(0);
+        for (size_t i = 0; i < bfs.size(); ++i)
+            for (uint32_t c = 0; c < nodes[bfs[i]].n_children; ++c) {
+                const uint32_t row = nodes[bfs[i]].first_child + c;
+                depth[row] = depth[bfs[i]] + 1;
+                bfs.push_back(row);
+            }
+        if (bfs.size() != n_nodes) return fail(CLS_E_BAD_TREE, "cls_pair_host: rows unreachable from the root");
+        std::sort(by_id.begin(), by_id.end());
+        for (uint32_t r = 1; r < n_nodes; ++r)
+            if (by_id[r].first == by_id[r - 1].first) return fail(CLS_E_BAD_TREE, "cls_pair_host: duplicate clade id " + std::to_string(by_id[r].first));
+        auto usable_row = [&](const cls_placement& m) -> uint32_t {
+            if (m.status != CLS_IDENTITY_FOUND && m.status != CLS_MAX_RESOLUTION && m.status != CLS_INCONCLUSIVE) return NONE;
+            auto it = std::lower_bound(by_id.begin(), by_id.end(), std::make_pair((uint64_t)m.clade_id, (uint32_t)0));
+            return (it == by_id.end() || it->first != m.clade_id) ? NONE : it->second;
+        };
+        auto copy = [](cls_placement& dst, const cls_placement& src) {
+            memset(&dst, 0, sizeof dst);
+            dst.status = src.status; dst.one = src.one; dst.rest = src.rest; dst.levels = src.levels; dst.clade_id = src.clade_id;
+        };
+        const bool conservative = flags & CLS_PAIR_CONSERVATIVE, require_both = flags & CLS_PAIR_REQUIRE_BOTH;
+        for (uint64_t i = 0; i < n; ++i) {
+            const cls_placement &m1 = a[i * stride], &m2 = b[i * stride];
+            const uint32_t r1 = usable_row(m1), r2 = usable_row(m2);
+            uint8_t klass;
+            cls_placement& P = out[i];
+            if (r1 == NONE && r2 == NONE) { klass = CLS_PAIR_NEITHER; copy(P, m1); }
+            else if (r2 == NONE) { klass = CLS_PAIR_ONLY_1; copy(P, require_both ? m2 : m1); }
+            else if (r1 == NONE) { klass = CLS_PAIR_ONLY_2; copy(P, require_both ? m1 : m2); }
+            else if (r1 == r2) {
+                klass = CLS_PAIR_SAME;
+                bool second = false;
+                if (m2.status != m1.status) second = m2.status < m1.status;
+                else if (m2.one != m1.one) second = m2.one > m1.one;
+                else if (m2.rest != m1.rest) second = m2.rest < m1.rest;
+                copy(P, second ? m2 : m1);
+            } else {
+                uint32_t x = r1, y = r2;
+                while (depth[x] > depth[y]) x = parent_row[x];
+                while (depth[y] > depth[x]) y = parent_row[y];
+                while (x != y) { x = parent_row[x]; y = parent_row[y]; }
+                if (x == r2) { klass = CLS_PAIR_NESTED_1; copy(P, conservative ? m2 : m1); }       // mate 1 lies below mate 2
+                else if (x == r1) { klass = CLS_PAIR_NESTED_2; copy(P, conservative ? m1 : m2); }
+                else {
+                    klass = CLS_PAIR_DISCORDANT;
+                    memset(&P, 0, sizeof P);
+                    P.status = CLS_MAX_RESOLUTION;
+                    P.levels = depth[x];
+                    P.clade_id = nodes[x].id;
+                }
+            }
+            if (how) how[i] = klass;
+            if (totals) { totals->n_pairs++; totals->how_count[klass]++; }
+        }
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CLS_E_NOMEM, "cls_pair_host: out of host memory");
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_pair_host: unknown exception");
+    }
+}
+
+extern "C" int cls_pair_names_host(const char* headers1, const uint64_t* off1, const char* headers2, const uint64_t* off2, uint32_t stride,
+                                   uint64_t n, uint64_t* n_bad, uint64_t* first_bad) {
+    if (!n_bad || !first_bad || (n && (!headers1 || !off1 || !headers2 || !off2))) return fail(CLS_E_INVALID_ARG, "cls_pair_names_host: null argument");
+    if (stride != 1 && stride != 2) return fail(CLS_E_INVALID_ARG, "cls_pair_names_host: stride must be 1 or 2");
+    *n_bad = 0;
+    *first_bad = UINT64_MAX;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t r = i * stride;
+        const char *h1 = headers1 + off1[r], *h2 = headers2 + off2[r];
+        const uint64_t l1 = cls::pair_name_len(h1, off1[r + 1] - off1[r]), l2 = cls::pair_name_len(h2, off2[r + 1] - off2[r]);
+        if (l1 == l2 && memcmp(h1, h2, l1) == 0) continue;
+        if (*n_bad == 0) *first_bad = i;
+        ++*n_bad;
+    }
+    return CLS_OK;
+}
+
+// The name kernel on `stream` with a result buffer of its own; synchronises `stream`.
+static int pair_names_on(const void* d_headers1, const void* d_off1, const void* d_headers2, const void* d_off2, uint32_t stride, uint32_t n,
+                         uint64_t* n_bad, uint64_t* first_bad, hipStream_t stream) {
+    *n_bad = 0;
+    *first_bad = UINT64_MAX;
+    if (n == 0) return CLS_OK;
+    unsigned long long* d_res = nullptr;
+    unsigned long long res[2] = {0, ~0ull};
+    hipError_t e = hipMalloc((void**)&d_res, sizeof res);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string("cls_pair_names_device: ") + hipGetErrorString(e));
+    if ((e = hipMemcpyAsync(d_res, res, sizeof res, hipMemcpyHostToDevice, stream)) == hipSuccess &&
+        (e = hipStreamSynchronize(stream)) == hipSuccess &&  // (`res` is reused for the way back)
+        (e = cls::launch_pair_names((const char*)d_headers1, (const uint64_t*)d_off1, (const char*)d_headers2, (const uint64_t*)d_off2, stride, n,
+                                    d_res, stream)) == hipSuccess &&
+        (e = hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, stream)) == hipSuccess)
+        e = hipStreamSynchronize(stream);
+    (void)hipFree(d_res);
+    if (e != hipSuccess) return fail(CLS_E_HIP, std::string("cls_pair_names_device: ") + hipGetErrorString(e));
+    *n_bad = res[0];
+    *first_bad = res[1];
+    return CLS_OK;
+}
+
+extern "C" int cls_pair_names_device(const void* d_headers1, const void* d_off1, const void* d_headers2, const void* d_off2, uint32_t stride,
+                                     uint32_t n, uint64_t* n_bad, uint64_t* first_bad, void* hip_stream) {
+    if (!n_bad || !first_bad || (n && (!d_off1 || !d_off2))) return fail(CLS_E_INVALID_ARG, "cls_pair_names_device: null argument");
+    if (stride != 1 && stride != 2) return fail(CLS_E_INVALID_ARG, "cls_pair_names_device: stride must be 1 or 2");
+    return pair_names_on(d_headers1, d_off1, d_headers2, d_off2, stride, n, n_bad, first_bad, (hipStream_t)hip_stream);
+}
+
+// Paired FASTQ text -> P (and `how`), all on the device; see cls_place_fastq_pairs_text in cls_place.h.  With `tally`
+// P is added to it on the device instead and nothing per read is copied back (`fa` carries n and truncated only).
+static int pairs_text(const char* who, cls_db* db, cls_pairer* p, cls_tally* tally, const char* text1, size_t len1, const char* text2,
+                      size_t len2, const cls_params* params, const cls_fastq_opts* opts, uint32_t flags, cls_fasta* fa,
+                      cls_placement** records, uint8_t** how) {
+    if (!db || !p || !fa || (!records && !tally) || (!text1 && len1) || (!text2 && len2)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": null argument");
+    if (p->db != db) return fail(CLS_E_INVALID_ARG, std::string(who) + ": the pairer belongs to another handle");
+    if (tally && tally->db != db) return fail(CLS_E_INVALID_ARG, std::string(who) + ": the tally belongs to another handle");
+    const uint32_t stride = text2 ? 1u : 2u;
+    if (int rc = check_pair_flags(who, stride, flags)) return rc;
+    memset(fa, 0, sizeof *fa);
+    if (records) *records = nullptr;
+    if (how) *how = nullptr;
+    int prev = 0;
+    CLS_HIP(hipGetDevice(&prev));
+    CLS_HIP(hipSetDevice(db->device));
+    hipStream_t stream = nullptr;
+    void *d_text = nullptr, *d_bases = nullptr, *d_off = nullptr, *d_recs = nullptr, *d_P = nullptr, *d_how = nullptr, *d_hdr = nullptr, *d_new_off = nullptr;
+    cls_fasta_dev dv1, dv2;
+    memset(&dv1, 0, sizeof dv1);
+    memset(&dv2, 0, sizeof dv2);
+    cls_placement* recs = nullptr;
+    uint8_t* h_how = nullptr;
+    bool ok = false;
+    auto cleanup = [&]() {
+        for (void* x : {d_text, d_bases, d_off, d_recs, d_P, d_how, d_hdr, d_new_off}) if (x) (void)hipFree(x);
+        cls_fasta_dev_free(&dv1);
+        cls_fasta_dev_free(&dv2);
+        if (stream) (void)hipStreamDestroy(stream);
+        (void)hipSetDevice(prev);
+        if (!ok) { free(recs); free(h_how); cls_fasta_free(fa); }
+    };
+#define CLS_TRY(expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess) { cleanup(); return fail(e_ == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } \
+    } while (0)
+    try {
+        CLS_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        // ---- both texts to the device once, the FASTQ stage on each ------------------------------------------------
+        const char* texts[2] = {text1, text2};
+        const size_t lens[2] = {len1, len2};
+        cls_fasta_dev* dvs[2] = {&dv1, &dv2};
+        for (int m = 0; m < (text2 ? 2 : 1); ++m) {
+            CLS_TRY(hipMalloc(&d_text, lens[m] ? lens[m] : 16));
+            if (lens[m]) CLS_TRY(hipMemcpyAsync(d_text, texts[m], lens[m], hipMemcpyHostToDevice, stream));
+            const int rc = cls_fastq_scan_device(d_text, lens[m], opts, dvs[m], stream);
+            if (rc != CLS_OK) { cleanup(); return rc; }
+            (void)hipFree(d_text);
+            d_text = nullptr;
+        }
+        if (text2 && dv1.n != dv2.n) {
+            const std::string msg = std::string(who) + ": the mate files hold different numbers of records (" + std::to_string(dv1.n) + " and " +
+                                    std::to_string(dv2.n) + ")";
+            cleanup();
+            return fail(CLS_E_BAD_PAIRS, msg);
+        }
+        if (!text2 && (dv1.n & 1u)) {
+            const std::string msg = std::string(who) + ": the interleaved text holds an odd number of records (" + std::to_string(dv1.n) + ")";
+            cleanup();
+            return fail(CLS_E_BAD_PAIRS, msg);
+        }
+        const uint64_t n64 = text2 ? dv1.n : dv1.n / 2;
+        if (n64 > 0x7FFFFFFFull) { cleanup(); return fail(CLS_E_BAD_PAIRS, std::string(who) + ": more than 2^31 - 1 pairs"); }
+        const uint32_t n = (uint32_t)n64;
+        const uint64_t n_reads = 2 * n64;
+        fa->n = n;
+        fa->truncated = dv1.truncated | dv2.truncated;
+        // ---- the name check ------------------------------------------------------------------------------------------
+        const char* d_h2 = (const char*)(text2 ? dv2.d_headers : dv1.d_headers);
+        const uint64_t* d_o1 = (const uint64_t*)dv1.d_header_off;
+        const uint64_t* d_o2 = text2 ? (const uint64_t*)dv2.d_header_off : d_o1 + 1;
+        uint64_t n_bad = 0, first_bad = 0;
+        int rc = pair_names_on(dv1.d_headers, d_o1, d_h2, d_o2, stride, n, &n_bad, &first_bad, stream);
+        if (rc != CLS_OK) { cleanup(); return rc; }
+        if (n_bad) {
+            std::string names[2];
+            const char* hs[2] = {(const char*)dv1.d_headers, d_h2};
+            const uint64_t* os[2] = {d_o1, d_o2};
+            for (int m = 0; m < 2; ++m) {
+                uint64_t o[2];
+                CLS_TRY(hipMemcpy(o, os[m] + first_bad * stride, sizeof o, hipMemcpyDeviceToHost));
+                std::string h(o[1] - o[0], '\0');
+                if (!h.empty()) CLS_TRY(hipMemcpy(&h[0], hs[m] + o[0], h.size(), hipMemcpyDeviceToHost));
+                names[m] = h.substr(0, cls::pair_name_len(h.data(), h.size()));
+            }
+            const std::string msg = std::string(who) + ": the mates' names disagree in " + std::to_string(n_bad) + " pair(s), first at pair " +
+                                    std::to_string(first_bad) + ": \"" + names[0] + "\" and \"" + names[1] + "\"";
+            cleanup();
+            return fail(CLS_E_BAD_PAIRS, msg);
+        }
+        // ---- one batch of 2 n reads: R1's bases then R2's, or the interleaved batch as it is ----------------------------
+        std::vector<uint64_t> boff(n_reads + 1);
+        CLS_TRY(hipMemcpyAsync(boff.data(), dv1.d_base_off, ((size_t)dv1.n + 1) * 8, hipMemcpyDeviceToHost, stream));
+        const void* d_all_bases = dv1.d_bases;
+        const uint64_t* d_all_off = (const uint64_t*)dv1.d_base_off;
+        if (text2) {
+            CLS_TRY(hipMemcpyAsync(boff.data() + n, dv2.d_base_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
+            CLS_TRY(hipStreamSynchronize(stream));
+            for (uint64_t i = n; i <= n_reads; ++i) boff[i] += dv1.n_bases;  // (boff[n] was R1's end, is R2's first offset + that)
+            CLS_TRY(hipMalloc(&d_bases, dv1.n_bases + dv2.n_bases + 16));
+            CLS_TRY(hipMalloc(&d_off, (n_reads + 1) * 8));
+            if (dv1.n_bases) CLS_TRY(hipMemcpyAsync(d_bases, dv1.d_bases, dv1.n_bases, hipMemcpyDeviceToDevice, stream));
+            if (dv2.n_bases) CLS_TRY(hipMemcpyAsync((char*)d_bases + dv1.n_bases, dv2.d_bases, dv2.n_bases, hipMemcpyDeviceToDevice, stream));
+            CLS_TRY(hipMemcpyAsync(d_off, boff.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice, stream));
+            d_all_bases = d_bases;
+            d_all_off = (const uint64_t*)d_off;
+        }
+        CLS_TRY(hipStreamSynchronize(stream));
+        if (n) {
+            CLS_TRY(hipMalloc(&d_recs, n_reads * sizeof(cls_placement)));
+            CLS_TRY(hipMalloc(&d_P, (size_t)n * sizeof(cls_placement)));
+            CLS_TRY(hipMalloc(&d_how, n));
+        }
+        const uint64_t max_reads = 16u << 20;  // bounds the per-call scratch (class lists, sort keys): one call up to 8 M pairs
+        for (uint64_t first = 0; first < n_reads; first += max_reads) {
+            const uint32_t cnt = (uint32_t)std::min(max_reads, n_reads - first);
+            uint64_t longest = 1;  // (the classes beyond the chunk's longest read are not launched)
+            uint32_t n_long = 1;
+            for (uint32_t i = 0; i < cnt; ++i) {
+                const uint64_t l = boff[first + i + 1] - boff[first + i];
+                const uint64_t nk = l < db->dev.k ? 0 : 2 * (l - db->dev.k + 1);
+                longest = std::max(longest, std::min(l, HARD_MAX_READ_LEN));
+                if (nk > cls::MAX_READ_KMERS) ++n_long;
+            }
+            rc = place_device(db, d_all_bases, d_all_off + first, cnt, params, (cls_placement*)d_recs + first, nullptr, stream, (uint32_t)(2 * longest), n_long);
+            if (rc != CLS_OK) { cleanup(); return rc; }
+            CLS_TRY(hipStreamSynchronize(stream));
+        }
+        // ---- the pairing kernel, then what returns --------------------------------------------------------------------
+        if (n) {
+            const cls_placement* d_a = (const cls_placement*)d_recs;
+            rc = pair_on(p, d_a, stride == 2 ? d_a + 1 : d_a + n, stride, n, flags, d_P, d_how, stream, false);
+            if (rc != CLS_OK) { cleanup(); return rc; }
+        }
+        if (tally) {
+            if (n) {
+                rc = tally_add_on(tally, d_P, n, stream, false);
+                if (rc != CLS_OK) { cleanup(); return rc; }
+            }
+        } else {
+            fa->header_off = (uint64_t*)malloc(((size_t)n + 1) * 8);
+            recs = (cls_placement*)malloc(((size_t)n + 1) * sizeof(cls_placement));
+            h_how = (uint8_t*)malloc((size_t)n + 1);
+            if (!fa->header_off || !recs || !h_how) { cleanup(); return fail(CLS_E_NOMEM, std::string(who) + ": out of host memory"); }
+            uint64_t n_hdr = dv1.n_header_bytes;
+            const void* d_hdr_src = dv1.d_headers;
+            if (text2) CLS_TRY(hipMemcpyAsync(fa->header_off, dv1.d_header_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
+            else {
+                // mate 1's headers of an interleaved set: every second one, gathered on the device
+                std::vector<uint64_t> hoff(n_reads + 1);
+                CLS_TRY(hipMemcpyAsync(hoff.data(), dv1.d_header_off, (n_reads + 1) * 8, hipMemcpyDeviceToHost, stream));
+                CLS_TRY(hipStreamSynchronize(stream));
+                fa->header_off[0] = 0;
+                for (uint32_t i = 0; i < n; ++i) fa->header_off[i + 1] = fa->header_off[i] + (hoff[2 * (size_t)i + 1] - hoff[2 * (size_t)i]);
+                n_hdr = fa->header_off[n];
+                CLS_TRY(hipMalloc(&d_new_off, ((size_t)n + 1) * 8));
+                CLS_TRY(hipMalloc(&d_hdr, n_hdr + 16));
+                CLS_TRY(hipMemcpyAsync(d_new_off, fa->header_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, stream));
+                CLS_TRY(cls::launch_pair_gather_headers((const char*)dv1.d_headers, d_o1, 2, n, (const uint64_t*)d_new_off, (char*)d_hdr, stream));
+                d_hdr_src = d_hdr;
+            }
+            fa->headers = (char*)malloc(n_hdr + 1);
+            if (!fa->headers) { cleanup(); return fail(CLS_E_NOMEM, std::string(who) + ": out of host memory"); }
+            if (n_hdr) CLS_TRY(hipMemcpyAsync(fa->headers, d_hdr_src, n_hdr, hipMemcpyDeviceToHost, stream));
+            if (n) {
+                CLS_TRY(hipMemcpyAsync(recs, d_P, (size_t)n * sizeof(cls_placement), hipMemcpyDeviceToHost, stream));
+                CLS_TRY(hipMemcpyAsync(h_how, d_how, n, hipMemcpyDeviceToHost, stream));
+            }
+        }
+        CLS_TRY(hipStreamSynchronize(stream));
+        if (records) *records = recs; else free(recs);
+        if (how) *how = h_how; else free(h_how);
+        ok = true;
+        cleanup();
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        cleanup();
+        return fail(CLS_E_NOMEM, std::string(who) + ": out of host memory");
+    } catch (...) {
+        cleanup();
+        return fail(CLS_E_INTERNAL, std::string(who) + ": unknown exception");
+    }
+#undef CLS_TRY
+}
+
+extern "C" int cls_place_fastq_pairs_text(cls_db* db, cls_pairer* p, const char* text1, size_t len1, const char* text2, size_t len2,
+                                          const cls_params* params, const cls_fastq_opts* opts, uint32_t flags, cls_fasta* fa,
+                                          cls_placement** records, uint8_t** how) {
+    if (!records) return fail(CLS_E_INVALID_ARG, "cls_place_fastq_pairs_text: null argument");
+    return pairs_text("cls_place_fastq_pairs_text", db, p, nullptr, text1, len1, text2, len2, params, opts, flags, fa, records, how);
+}
+
+extern "C" int cls_tally_fastq_pairs_text(cls_db* db, cls_pairer* p, cls_tally* tally, const char* text1, size_t len1, const char* text2,
+                                          size_t len2, const cls_params* params, const cls_fastq_opts* opts, uint32_t flags,
+                                          uint32_t* n_pairs, uint32_t* truncated) {
+    if (!tally) return fail(CLS_E_INVALID_ARG, "cls_tally_fastq_pairs_text: null tally");
+    cls_fasta fa;
+    const int rc = pairs_text("cls_tally_fastq_pairs_text", db, p, tally, text1, len1, text2, len2, params, opts, flags, &fa, nullptr, nullptr);
+    if (rc != CLS_OK) return rc;
+    if (n_pairs) *n_pairs = fa.n;
     if (truncated) *truncated = fa.truncated;
     return CLS_OK;
 }

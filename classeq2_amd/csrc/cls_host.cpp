@@ -1153,3 +1153,98 @@ extern "C" int cls_profile_sequences_group(cls_db_group* grp, const cls_tree* t,
         return fail(CLS_E_INTERNAL, "cls_profile_sequences_group: unknown exception");
     }
 }
+
+// ---- paired-end use-case ---------------------------------------------------------------------------------------------
+
+static const char* const PAIR_CLASS_NAMES[7] = {"NEITHER", "ONLY_1", "ONLY_2", "SAME", "NESTED_1", "NESTED_2", "DISCORDANT"};
+
+extern "C" int cls_place_pairs(cls_db* db, const cls_tree* t, const char* query1, const char* query2, const char* out_file,
+                               const char* report_path, const char* summary_path, const cls_params* params, const cls_fastq_opts* opts,
+                               uint32_t flags, int format, int overwrite, int all_rows, uint32_t* n_pairs, double* seconds) {
+    if (!db || !t || !query1) return fail(CLS_E_INVALID_ARG, "cls_place_pairs: null argument");
+    if (!out_file && !report_path && !summary_path) return fail(CLS_E_INVALID_ARG, "cls_place_pairs: no output was asked for");
+    if (format != CLS_FORMAT_YAML && format != CLS_FORMAT_JSONL) return fail(CLS_E_INVALID_ARG, "cls_place_pairs: unknown output format");
+    struct Guard {
+        FILE *fo = nullptr, *fe = nullptr;
+        cls_placement* recs = nullptr;
+        uint8_t* how = nullptr;
+        cls_fasta fa{};
+        cls_pairer* pairer = nullptr;
+        cls_tally* tally = nullptr;
+        ~Guard() {
+            if (fo) fclose(fo);
+            if (fe) fclose(fe);
+            free(recs); free(how); cls_fasta_free(&fa);
+            cls_tally_destroy(tally);
+            cls_pairer_destroy(pairer);
+        }
+    } g;
+    try {
+        if (report_path) if (int rc = check_report_path(report_path, overwrite)) return rc;
+        if (summary_path) if (int rc = check_report_path(summary_path, overwrite)) return rc;
+        if (out_file) {  // output paths + overwrite policy, as place_sequences_with
+            const std::string out_path = with_extension(out_file, format == CLS_FORMAT_YAML ? "yaml" : "jsonl");
+            const std::string err_path = with_extension(out_file, "error");
+            const size_t slash = out_path.find_last_of('/');
+            if (slash != std::string::npos && slash > 0) (void)mkdir(out_path.substr(0, slash).c_str(), 0777);
+            struct stat sb;
+            if (stat(out_path.c_str(), &sb) == 0) {
+                if (!overwrite) return fail(CLS_E_INVALID_ARG, "Could not overwrite existing file \"" + out_path + "\" when overwrite option is `false`.");
+                if (unlink(out_path.c_str()) != 0) return fail(CLS_E_INVALID_ARG, std::string("Could not remove file given ") + strerror(errno));
+            }
+            g.fo = fopen(out_path.c_str(), "ab");
+            g.fe = fopen(err_path.c_str(), "ab");
+            if (!g.fo || !g.fe) return fail(CLS_E_INVALID_ARG, "Unable to open file");
+        }
+        auto t0 = std::chrono::steady_clock::now();
+        std::string text1 = read_file(query1), text2;
+        if (query2) text2 = read_file(query2);
+        int rc = cls_pairer_create(db, &g.pairer);
+        if (rc != CLS_OK) return fail(rc, cls_last_error());
+        const char* t2 = query2 ? text2.data() : nullptr;
+        std::vector<cls_tally_row> rows(t->rows.size(), cls_tally_row{});
+        cls_tally_totals totals{};
+        uint32_t n = 0;
+        if (out_file) {
+            rc = cls_place_fastq_pairs_text(db, g.pairer, text1.data(), text1.size(), t2, text2.size(), params, opts, flags, &g.fa, &g.recs, &g.how);
+            if (rc != CLS_OK) return fail(rc, cls_last_error());
+            n = g.fa.n;
+            std::vector<std::string> po, pe;
+            serialize_pieces(t, g.fa.headers, g.fa.header_off, n, g.recs, format, po, pe);
+            for (auto& x : po) if (!x.empty() && fwrite(x.data(), 1, x.size(), g.fo) != x.size()) return fail(CLS_E_INTERNAL, "Error writing to file");
+            for (auto& x : pe) if (!x.empty() && fwrite(x.data(), 1, x.size(), g.fe) != x.size()) return fail(CLS_E_INTERNAL, "Error writing to file");
+            if (report_path) {  // counted on the host from the records the run has anyway
+                rc = cls_tally_host(t->rows.data(), (uint32_t)t->rows.size(), g.recs, n, rows.data(), &totals);
+                if (rc != CLS_OK) return fail(rc, cls_last_error());
+            }
+        } else {  // nothing per pair leaves the device
+            rc = cls_tally_create(db, &g.tally);
+            if (rc != CLS_OK) return fail(rc, cls_last_error());
+            rc = cls_tally_fastq_pairs_text(db, g.pairer, g.tally, text1.data(), text1.size(), t2, text2.size(), params, opts, flags, &n, nullptr);
+            if (rc != CLS_OK) return fail(rc, cls_last_error());
+            if (report_path) {
+                rc = cls_tally_read(g.tally, rows.data(), (uint32_t)rows.size(), &totals);
+                if (rc != CLS_OK) return fail(rc, cls_last_error());
+            }
+        }
+        if (report_path) if ((rc = write_report(t, rows.data(), &totals, all_rows, report_path)) != CLS_OK) return rc;
+        if (summary_path) {
+            cls_pair_totals pt;
+            rc = cls_pairer_totals(g.pairer, &pt, 0);
+            if (rc != CLS_OK) return fail(rc, cls_last_error());
+            std::string o = "n_pairs\t" + std::to_string(pt.n_pairs) + "\n";
+            for (int s = 0; s < 7; ++s) o += std::string(PAIR_CLASS_NAMES[s]) + "\t" + std::to_string(pt.how_count[s]) + "\n";
+            FILE* f = fopen(summary_path, "wb");
+            if (!f) return fail(CLS_E_INVALID_ARG, std::string("Unable to open file ") + summary_path);
+            const bool ok = fwrite(o.data(), 1, o.size(), f) == o.size();
+            if (fclose(f) != 0 || !ok) return fail(CLS_E_INTERNAL, "Error writing to file");
+        }
+        if (n_pairs) *n_pairs = n;
+        if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return CLS_OK;
+    } catch (const std::exception& ex) {
+        return fail(CLS_E_INTERNAL, std::string("cls_place_pairs: ") + ex.what());
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_place_pairs: unknown exception");
+    }
+}

@@ -3,6 +3,8 @@
 //   cls-place [QUERY|-] -d DB -o OUT [-a ANNOTATIONS.yaml] [--out-format yaml|jsonl]
 //             [-i N] [-m COV] [-r] [-f] [--device N[,N...]] [--query-format fasta|fastq] [-q [5P,]3P]
 //             [--report PATH | --report-only PATH] [--report-all-clades]
+//             [-2 MATES | --interleaved] [--pair-mode deepest|conservative] [--pair-require-both] [--pair-summary PATH]
+// -2 / --interleaved place paired-end FASTQ: one result per pair, under mate 1's header (include/cls_host.h).
 // --report also writes the per-clade abundance profile of the run (include/cls_host.h "clade report"); --report-only
 // writes nothing else: the reads are tallied on the device and no per-read output exists (-o is then not needed).
 // The database is read like load_database does (ports/lib/src/functions/load_database.rs:9-53): the `.cls`
@@ -38,7 +40,13 @@ static void usage() {
             "                                      it), per status, unplaced reads by reason (tab-separated text)\n"
             "      --report-only <PATH>            write only the clade report: the reads are counted on the GPU, no per-read\n"
             "                                      result or .error file is written and -o is not required\n"
-            "      --report-all-clades             list every clade in the report, not only those with reads\n");
+            "      --report-all-clades             list every clade in the report, not only those with reads\n"
+            "  -2, --mate-file <PATH>              fastq only: QUERY holds the first mates, PATH the second; one result per pair\n"
+            "      --interleaved                   fastq only: QUERY holds the pairs' mates in turn\n"
+            "      --pair-mode <deepest|conservative>  mates placed at a clade and at its ancestor: keep the deeper one, or\n"
+            "                                      the ancestor [default: deepest]\n"
+            "      --pair-require-both             leave a pair unplaced unless both mates are placed\n"
+            "      --pair-summary <PATH>           write the pair classes (tab-separated name, count)\n");
 }
 
 // cutadapt's -q: "3P" or "5P,3P", each a cutoff in 0 .. 2^31 - 1
@@ -63,6 +71,8 @@ int main(int argc, char** argv) {
     std::vector<int> devices;  // --device with a comma: an index group, one replica per entry
     std::string qfmt = "fasta", trim, report, report_only;
     int all_rows = 0;
+    std::string mate_file, pair_mode, pair_summary;
+    bool interleaved = false, pair_require_both = false;
     cls_fastq_opts fq;
     memset(&fq, 0, sizeof fq);
     for (int i = 1; i < argc; ++i) {
@@ -101,6 +111,11 @@ int main(int argc, char** argv) {
         else if (a == "--report") report = need("--report");
         else if (a == "--report-only") report_only = need("--report-only");
         else if (a == "--report-all-clades") all_rows = 1;
+        else if (a == "-2" || a == "--mate-file") mate_file = need("--mate-file");
+        else if (a == "--interleaved") interleaved = true;
+        else if (a == "--pair-mode") pair_mode = need("--pair-mode");
+        else if (a == "--pair-require-both") pair_require_both = true;
+        else if (a == "--pair-summary") pair_summary = need("--pair-summary");
         else if (!a.empty() && a[0] == '-' && a != "-") { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); usage(); return 2; }
         else query = a;
     }
@@ -113,6 +128,24 @@ int main(int argc, char** argv) {
         if (!parse_cutoffs(trim, &fq.trim_5p, &fq.trim_3p)) { fprintf(stderr, "error: invalid value '%s' for '--trim-quality'\n", trim.c_str()); return 2; }
     }
     const int query_format = qfmt == "fastq" ? CLS_QUERY_FASTQ : CLS_QUERY_FASTA;
+    const bool pairs = !mate_file.empty() || interleaved;
+    if (!pairs && (!pair_mode.empty() || pair_require_both || !pair_summary.empty())) {
+        fprintf(stderr, "error: the '--pair-...' options need '--mate-file' or '--interleaved'\n");
+        return 2;
+    }
+    uint32_t pair_flags = 0;
+    if (pairs) {
+        if (qfmt != "fastq") { fprintf(stderr, "error: paired reads need '--query-format fastq'\n"); return 2; }
+        if (!mate_file.empty() && interleaved) { fprintf(stderr, "error: '--mate-file' cannot be used with '--interleaved'\n"); return 2; }
+        if (!devices.empty()) { fprintf(stderr, "error: paired reads are placed on one device: '--device' takes one ordinal\n"); return 2; }
+        if (!pair_mode.empty() && pair_mode != "deepest" && pair_mode != "conservative") {
+            fprintf(stderr, "error: invalid value '%s' for '--pair-mode'\n", pair_mode.c_str());
+            return 2;
+        }
+        if (query == "-") { fprintf(stderr, "error: paired reads are read from files\n"); return 2; }
+        if (pair_mode == "conservative") pair_flags |= CLS_PAIR_CONSERVATIVE;
+        if (pair_require_both) pair_flags |= CLS_PAIR_REQUIRE_BOTH;
+    }
 
     cls_tree* tree = nullptr;
     if (cls_tree_load(db_path.c_str(), &tree) != CLS_OK) { fprintf(stderr, "Error loading database: %s\n", cls_host_last_error()); return 1; }
@@ -134,7 +167,12 @@ int main(int argc, char** argv) {
     double seconds = 0;
     const int format = fmt == "yaml" ? CLS_FORMAT_YAML : CLS_FORMAT_JSONL;
     int rc;
-    if (!report_only.empty())
+    if (pairs) {
+        const std::string& rep = report_only.empty() ? report : report_only;
+        rc = cls_place_pairs(db, tree, query.c_str(), mate_file.empty() ? nullptr : mate_file.c_str(), report_only.empty() ? out_path.c_str() : nullptr,
+                             rep.empty() ? nullptr : rep.c_str(), pair_summary.empty() ? nullptr : pair_summary.c_str(), &p, &fq, pair_flags, format,
+                             overwrite, all_rows, &n, &seconds);
+    } else if (!report_only.empty())
         rc = db ? cls_profile_sequences(db, tree, query.c_str(), report_only.c_str(), &p, overwrite, query_format, &fq, 0, all_rows, &n, &seconds)
                 : cls_profile_sequences_group(group, tree, query.c_str(), report_only.c_str(), &p, overwrite, query_format, &fq, 0, all_rows, &n,
                                               &seconds);

@@ -30,12 +30,15 @@ EXPORTS = [
     "cls_place_fastq_text", "cls_last_error",
     "cls_tally_create", "cls_tally_destroy", "cls_tally_reset", "cls_tally_add_device", "cls_tally_add", "cls_tally_read", "cls_tally_host",
     "cls_tally_merge", "cls_tally_fasta_text", "cls_tally_fastq_text",
+    "cls_pairer_create", "cls_pairer_destroy", "cls_pairer_totals", "cls_pair_records_device", "cls_pair_records", "cls_pair_host",
+    "cls_pair_names_host", "cls_pair_names_device", "cls_place_fastq_pairs_text", "cls_tally_fastq_pairs_text",
     "cls_version", "cls_set_tuning", "cls_tuning_from_env", "cls_kmers_build", "cls_kmers_desc", "cls_kmers_info_get", "cls_kmers_free",
 ]
 HOST_EXPORTS = [
     "cls_tree_load_json", "cls_tree_load", "cls_tree_init_from_file", "cls_tree_from_newick", "cls_tree_serialize", "cls_tree_save", "cls_tree_free", "cls_tree_set_annotations_yaml", "cls_tree_build_kmers_map", "cls_tree_build_kmers_map_device", "cls_tree_desc", "cls_serialize_results",
     "cls_host_free", "cls_place_sequences", "cls_place_sequences_group", "cls_place_sequences_ex", "cls_place_sequences_group_ex",
     "cls_host_last_error", "cls_tally_report", "cls_profile_sequences", "cls_profile_sequences_group", "cls_place_sequences_report", "cls_tree_nodes",
+    "cls_place_pairs",
 ]
 SERVICE_EXPORTS = [
     "cls_service_create", "cls_service_destroy", "cls_service_add_model", "cls_service_submit", "cls_service_wait", "cls_service_pause",
@@ -133,6 +136,29 @@ def lib():
         L.cls_tally_fastq_text.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params), C.POINTER(_abi.FastqOpts), C.POINTER(u32),
                                            C.POINTER(u32)]
         L.cls_tally_fastq_text.restype = i32
+        u64 = C.c_uint64
+        L.cls_pairer_create.argtypes = [vp, C.POINTER(vp)]
+        L.cls_pairer_create.restype = i32
+        L.cls_pairer_destroy.argtypes = [vp]
+        L.cls_pairer_destroy.restype = None
+        L.cls_pairer_totals.argtypes = [vp, vp, i32]
+        L.cls_pairer_totals.restype = i32
+        L.cls_pair_records_device.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp]
+        L.cls_pair_records_device.restype = i32
+        L.cls_pair_records.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
+        L.cls_pair_records.restype = i32
+        L.cls_pair_host.argtypes = [vp, u32, vp, vp, u32, u64, u32, vp, vp, vp]
+        L.cls_pair_host.restype = i32
+        L.cls_pair_names_host.argtypes = [vp, vp, vp, vp, u32, u64, C.POINTER(u64), C.POINTER(u64)]
+        L.cls_pair_names_host.restype = i32
+        L.cls_pair_names_device.argtypes = [vp, vp, vp, vp, u32, u32, C.POINTER(u64), C.POINTER(u64), vp]
+        L.cls_pair_names_device.restype = i32
+        L.cls_place_fastq_pairs_text.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params),
+                                                 C.POINTER(_abi.FastqOpts), u32, C.POINTER(_abi.Fasta), C.POINTER(vp), C.POINTER(vp)]
+        L.cls_place_fastq_pairs_text.restype = i32
+        L.cls_tally_fastq_pairs_text.argtypes = [vp, vp, vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params),
+                                                 C.POINTER(_abi.FastqOpts), u32, C.POINTER(u32), C.POINTER(u32)]
+        L.cls_tally_fastq_pairs_text.restype = i32
         L.cls_fasta_free.argtypes = [C.POINTER(_abi.Fasta)]
         L.cls_fasta_free.restype = None
         L.cls_last_error.restype = C.c_char_p
@@ -199,6 +225,9 @@ def lib():
         L.cls_place_sequences_report.argtypes = [vp, vp, vp, C.c_char_p, C.c_char_p, C.POINTER(_abi.Params), i32, i32, i32, C.POINTER(_abi.FastqOpts),
                                                  C.c_char_p, i32, C.POINTER(u32), C.POINTER(C.c_double)]
         L.cls_place_sequences_report.restype = i32
+        L.cls_place_pairs.argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(_abi.Params),
+                                      C.POINTER(_abi.FastqOpts), u32, i32, i32, i32, C.POINTER(u32), C.POINTER(C.c_double)]
+        L.cls_place_pairs.restype = i32
         # resident batching service (include/cls_service.h)
         L.cls_service_create.argtypes = [C.POINTER(vp)]
         L.cls_service_create.restype = i32
@@ -484,6 +513,39 @@ class PlacementDb:
         _check(lib().cls_tally_fastq_text(self._h, tally._h, text, len(text), pp, C.byref(o), C.byref(n), C.byref(tr)))
         return n.value, bool(tr.value)
 
+    def place_fastq_pairs_text(self, pairer: "Pairer", text1: bytes, text2: Optional[bytes] = None, params: Optional[_abi.Params] = None,
+                               trim_5p: int = 0, trim_3p: int = 0, flags: int = 0):
+        """Paired FASTQ text (`text2` None: `text1` is interleaved) -> (mate 1's headers, P, how, truncated): both mates
+        placed as one batch and reconciled on the device (cls_place_fastq_pairs_text); the classes go to `pairer`."""
+        f = _abi.Fasta()
+        recs, how = C.c_void_p(), C.c_void_p()
+        pp = C.byref(params) if params is not None else None
+        o = _fastq_opts(trim_5p, trim_3p)
+        _check(lib().cls_place_fastq_pairs_text(self._h, pairer._h, text1, len(text1), text2, len(text2) if text2 is not None else 0, pp,
+                                                C.byref(o), flags, C.byref(f), C.byref(recs), C.byref(how)))
+        try:
+            n = f.n
+            hoff = np.ctypeslib.as_array(f.header_off, shape=(n + 1,)).copy()
+            hraw = C.string_at(f.headers, int(hoff[-1]))
+            headers = [hraw[int(hoff[i]) : int(hoff[i + 1])] for i in range(n)]
+            out = np.frombuffer(C.string_at(recs, n * 24), dtype=_abi.PLACEMENT_DTYPE).copy() if n else np.zeros(0, _abi.PLACEMENT_DTYPE)
+            hw = np.frombuffer(C.string_at(how, n), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
+            return headers, out, hw, bool(f.truncated)
+        finally:
+            lib().cls_fasta_free(C.byref(f))
+            lib().cls_host_free(recs)
+            lib().cls_host_free(how)
+
+    def tally_fastq_pairs_text(self, pairer: "Pairer", tally: "Tally", text1: bytes, text2: Optional[bytes] = None,
+                               params: Optional[_abi.Params] = None, trim_5p: int = 0, trim_3p: int = 0, flags: int = 0):
+        """The same pipeline with P added to `tally` on the device (cls_tally_fastq_pairs_text) -> (pairs, truncated)."""
+        n, tr = C.c_uint32(0), C.c_uint32(0)
+        pp = C.byref(params) if params is not None else None
+        o = _fastq_opts(trim_5p, trim_3p)
+        _check(lib().cls_tally_fastq_pairs_text(self._h, pairer._h, tally._h, text1, len(text1), text2, len(text2) if text2 is not None else 0,
+                                                pp, C.byref(o), flags, C.byref(n), C.byref(tr)))
+        return n.value, bool(tr.value)
+
     def set_max_read_len(self, n_bases: int) -> None:
         """Longest read place_batch_device() provisions for (cls_db_set_max_read_len)."""
         _check(lib().cls_db_set_max_read_len(self._h, n_bases))
@@ -565,6 +627,97 @@ def tally_merge(rows: np.ndarray, totals: np.ndarray, add_rows: np.ndarray, add_
     assert rows.dtype == _abi.TALLY_ROW_DTYPE and len(rows) == len(add_rows) and rows.flags.c_contiguous
     assert totals.dtype == _abi.TALLY_TOTALS_DTYPE and totals.shape == (1,)
     _check(lib().cls_tally_merge(rows.ctypes.data, totals.ctypes.data, add_rows.ctypes.data, add_totals.ctypes.data, len(rows)))
+
+
+class Pairer:
+    """Device-resident reconciler of paired reads bound to one PlacementDb (cls_pairer): the two mates' placement records
+    -> one record per pair plus a class byte; counts the classes over every call."""
+
+    def __init__(self, db: PlacementDb):
+        self._db = db  # (the pairer borrows the handle)
+        self._h = C.c_void_p()
+        _check(lib().cls_pairer_create(db._h, C.byref(self._h)))
+
+    def pair_device(self, d_a: int, d_b: int, stride: int, n: int, d_out: int, d_how: int = 0, flags: int = 0, stream: int = 0) -> None:
+        """Device pointers in / out, asynchronous on `stream` (cls_pair_records_device)."""
+        _check(lib().cls_pair_records_device(self._h, d_a or None, d_b or None, stride, n, flags, d_out or None, d_how or None, stream or None))
+
+    def pair(self, a: np.ndarray, b: Optional[np.ndarray] = None, flags: int = 0):
+        """Host records through the kernel (cls_pair_records) -> (P, how).  `b` None: `a` is interleaved."""
+        return _pair_call(lambda *args: lib().cls_pair_records(self._h, *args), a, b, flags, totals=False)
+
+    def totals(self, reset: bool = False):
+        """-> PAIR_TOTALS_DTYPE scalar; waits for the launches in flight (cls_pairer_totals)."""
+        t = np.zeros(1, dtype=_abi.PAIR_TOTALS_DTYPE)
+        _check(lib().cls_pairer_totals(self._h, t.ctypes.data, 1 if reset else 0))
+        return t[0]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().cls_pairer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _pair_call(fn, a, b, flags, totals):
+    """Shared argument plumbing of pair_host / Pairer.pair: `b` None means `a` holds interleaved records (stride 2)."""
+    a = np.ascontiguousarray(a, dtype=_abi.PLACEMENT_DTYPE)
+    if b is None:
+        if len(a) % 2:
+            raise ValueError("an interleaved batch holds an even number of records")
+        stride, n, pb = 2, len(a) // 2, a.ctypes.data + 24
+    else:
+        b = np.ascontiguousarray(b, dtype=_abi.PLACEMENT_DTYPE)
+        if len(a) != len(b):
+            raise ValueError("the two mates' record arrays differ in length")
+        stride, n, pb = 1, len(a), b.ctypes.data
+    out = np.full(n, 0xFF, dtype=np.uint8).repeat(24).view(_abi.PLACEMENT_DTYPE)  # (pad bytes must come back as 0)
+    how = np.full(n, 0xFF, dtype=np.uint8)
+    if totals:
+        tot = np.zeros(1, dtype=_abi.PAIR_TOTALS_DTYPE)
+        _check(fn(a.ctypes.data, pb, stride, n, flags, out.ctypes.data, how.ctypes.data, tot.ctypes.data))
+        return out, how, tot[0]
+    _check(fn(a.ctypes.data, pb, stride, n, flags, out.ctypes.data, how.ctypes.data))
+    return out, how
+
+
+def pair_host(flat, a: np.ndarray, b: Optional[np.ndarray] = None, flags: int = 0):
+    """The pairing rule on the host, no device (cls_pair_host) -> (P, how, totals).  `b` None: `a` is interleaved."""
+    nodes = np.ascontiguousarray(flat.nodes, dtype=_abi.NODE_DTYPE)
+    return _pair_call(lambda *args: lib().cls_pair_host(nodes.ctypes.data, len(nodes), *args), a, b, flags, totals=True)
+
+
+def pair_names_host(headers1, headers2=None):
+    """The mate-name rule on the host (cls_pair_names_host) -> (disagreeing pairs, lowest disagreeing index or None).
+    `headers2` None: `headers1` is an interleaved list (mates alternate)."""
+    def pack(hs):
+        hb = [h if isinstance(h, bytes) else h.encode() for h in hs]
+        return b"".join(hb), np.concatenate([[0], np.cumsum([len(h) for h in hb])]).astype(np.uint64)
+
+    t1, o1 = pack(headers1)
+    if headers2 is None:
+        if len(headers1) % 2:
+            raise ValueError("an interleaved list holds an even number of headers")
+        t2, p2, stride, n = t1, o1.ctypes.data + 8, 2, len(headers1) // 2
+    else:
+        if len(headers1) != len(headers2):
+            raise ValueError("the two header lists differ in length")
+        t2, o2 = pack(headers2)
+        p2, stride, n = o2.ctypes.data, 1, len(headers1)
+    n_bad, first = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().cls_pair_names_host(t1, o1.ctypes.data, t2, p2, stride, n, C.byref(n_bad), C.byref(first)))
+    return n_bad.value, (first.value if n_bad.value else None)
 
 
 class _ReplicaView(PlacementDb):
@@ -797,6 +950,20 @@ def place_sequences(db, tree: Tree, query_path: str, out_file: str, params: Opti
     fn = lib().cls_place_sequences_group_ex if group else lib().cls_place_sequences_ex
     _check_host(fn(db._h, tree._h, query_path.encode(), out_file.encode(), pp, 1 if overwrite else 0, fmt, _abi.QUERY_FASTQ, C.byref(o),
                    C.byref(n), C.byref(sec)))
+    return n.value, sec.value
+
+
+def place_pairs(db: PlacementDb, tree: Tree, query1: str, query2: Optional[str] = None, out_file: Optional[str] = None,
+                report_path: Optional[str] = None, summary_path: Optional[str] = None, params: Optional[_abi.Params] = None,
+                trim_quality=None, flags: int = 0, fmt: int = FORMAT_YAML, overwrite: bool = False, all_rows: bool = False):
+    """The paired-end use-case (cls_place_pairs): FASTQ mate files (`query2` None: `query1` is interleaved) -> per-pair
+    result / error files, the clade report and the pair summary, each optional -> (pairs, seconds)."""
+    n, sec = C.c_uint32(0), C.c_double(0)
+    o = _fastq_opts(*_trim_pair(trim_quality))
+    enc = lambda x: x.encode() if x is not None else None
+    _check_host(lib().cls_place_pairs(db._h, tree._h, query1.encode(), enc(query2), enc(out_file), enc(report_path), enc(summary_path),
+                                      C.byref(params) if params is not None else None, C.byref(o), flags, fmt, 1 if overwrite else 0,
+                                      1 if all_rows else 0, C.byref(n), C.byref(sec)))
     return n.value, sec.value
 
 

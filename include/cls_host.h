@@ -137,6 +137,21 @@ int cls_place_sequences_report(cls_db* db, cls_db_group* g, const cls_tree* t, c
                                const cls_fastq_opts* fastq, const char* report_path, int all_rows, uint32_t* n_placed,
                                double* seconds);
 
+/* ---- paired-end use-case: FASTQ mate files -> one placement per pair ----------------------------------------------
+ * `query1` / `query2`: the R1 / R2 files; `query2` == NULL: `query1` is interleaved.  The reads go through
+ * cls_place_fastq_pairs_text (cls_place.h "paired reads": one placement batch, the mate-name check, the pairing rule
+ * with `flags`) on one handle.  Every output is optional (at least one is needed):
+ *   out_file      per-pair result + error files through the existing serialiser, under mate 1's headers as they are
+ *                 (extension and overwrite policy as cls_place_sequences);
+ *   report_path   the clade report (cls_tally_report) over the tally of the pairs' records -- a fragment counts once;
+ *   summary_path  tab-separated "name\tcount" lines: n_pairs, then NEITHER, ONLY_1, ONLY_2, SAME, NESTED_1, NESTED_2,
+ *                 DISCORDANT.
+ * Without `out_file` nothing per pair leaves the device (cls_tally_fastq_pairs_text).  Mates that do not line up:
+ * CLS_E_BAD_PAIRS.  `n_pairs`, `seconds` may be NULL. */
+int cls_place_pairs(cls_db* db, const cls_tree* t, const char* query1, const char* query2, const char* out_file,
+                    const char* report_path, const char* summary_path, const cls_params* params, const cls_fastq_opts* opts,
+                    uint32_t flags, int format, int overwrite, int all_rows, uint32_t* n_pairs, double* seconds);
+
 const char* cls_host_last_error(void);
 
 #ifdef __cplusplus

@@ -40,6 +40,7 @@ extern "C" {
 #define CLS_E_HIP (-5)           /* a HIP runtime call failed                    */
 #define CLS_E_NOMEM (-6)
 #define CLS_E_INTERNAL (-7)
+#define CLS_E_BAD_PAIRS (-8)     /* paired input whose mates do not line up      */
 
 /* ---- tree: Clade (core/src/domain/dtos/clade.rs:18-38) ------------------ */
 /* NodeType, clade.rs:5-16.  LEAF-ness is decided by `kind` only
@@ -497,6 +498,95 @@ int cls_tally_fasta_text(cls_db* db, cls_tally* t, const char* text, size_t len,
                          uint32_t* n, uint32_t* truncated);
 int cls_tally_fastq_text(cls_db* db, cls_tally* t, const char* text, size_t len, const cls_params* params,
                          const cls_fastq_opts* opts, uint32_t* n, uint32_t* truncated);
+
+/* ---- paired reads: the two mates' placements -> one record per pair ------------------------
+ * Inputs: two record sequences, mate 1 = a[i * stride], mate 2 = b[i * stride] for i < n, stride 1 or 2.  Stride 2 with
+ * b = a + 1 is an interleaved batch; stride 1 with b = a + n is "all of R1, then all of R2".  Outputs: one cls_placement
+ * P[i] per pair (same layout: the tally, cls_serialize_results and the clade report work on P unchanged) and one class
+ * byte how[i].  Integer-only and exact:
+ *   - a mate is USABLE iff its status is CLS_IDENTITY_FOUND, CLS_MAX_RESOLUTION or CLS_INCONCLUSIVE and its clade_id is
+ *     a clade of the tree.  A status >= 12, another status or an unknown id makes it not usable; none is an error.
+ *   - "copy" = the fields status, one, rest, levels, clade_id; the pad bytes of P are always written as 0.
+ *   how                                   condition                                   P
+ *   CLS_PAIR_NEITHER                      neither mate usable                         copy of mate 1
+ *   CLS_PAIR_ONLY_1 / CLS_PAIR_ONLY_2     exactly that mate usable                    copy of the usable mate
+ *   CLS_PAIR_SAME                         both usable, same clade                     copy of the mate with the lower status
+ *                                                                                     value, then the larger `one`, then the
+ *                                                                                     smaller `rest`, then mate 1
+ *   CLS_PAIR_NESTED_1 / CLS_PAIR_NESTED_2 both usable, that mate's clade is a proper  copy of the descendant mate
+ *                                         descendant of the other's
+ *   CLS_PAIR_DISCORDANT                   both usable, neither clade holds the other  status = CLS_MAX_RESOLUTION, clade_id =
+ *                                                                                     id(LCA), one = rest = 0, levels = depth
+ *                                                                                     of the LCA in edges below the root
+ * Flags change P only, never `how`.  CLS_PAIR_CONSERVATIVE: in the NESTED classes copy the ancestor mate instead.
+ * CLS_PAIR_REQUIRE_BOTH: in the ONLY classes copy the mate that is NOT usable (the pair stays unplaced).  Any other
+ * flag bit is CLS_E_INVALID_ARG.
+ * Totals: 64-bit counters, associative over batches like the tally's. */
+enum {
+    CLS_PAIR_NEITHER = 0,
+    CLS_PAIR_ONLY_1 = 1,
+    CLS_PAIR_ONLY_2 = 2,
+    CLS_PAIR_SAME = 3,
+    CLS_PAIR_NESTED_1 = 4,
+    CLS_PAIR_NESTED_2 = 5,
+    CLS_PAIR_DISCORDANT = 6
+};
+#define CLS_PAIR_CONSERVATIVE 1u
+#define CLS_PAIR_REQUIRE_BOTH 2u
+
+typedef struct cls_pair_totals {
+    uint64_t n_pairs;
+    uint64_t how_count[8];            /* per CLS_PAIR_* class; entry 7 is unused, always 0 */
+} cls_pair_totals;                    /* 72 bytes */
+
+typedef struct cls_pairer cls_pairer; /* opaque; bound to one cls_db (a replica of a group included), lives on its device */
+
+/* A pairer with zeroed totals on the device of `db`.  It borrows the handle, like cls_tally: destroy it first. */
+int cls_pairer_create(cls_db* db, cls_pairer** out);
+void cls_pairer_destroy(cls_pairer* p);
+/* Waits for the launches in flight; `reset` != 0 zeroes the totals afterwards. */
+int cls_pairer_totals(cls_pairer* p, cls_pair_totals* totals, int reset);
+/* Records in the HBM of the handle's device, 8-byte aligned; stride 2 needs d_b = d_a + one record.  Asynchronous on
+ * `hip_stream`, in stream order; calls on different streams may overlap.  `d_out` (n records) must not alias the
+ * inputs; `d_how` (n bytes) may be NULL.  The classes are added to the pairer's totals. */
+int cls_pair_records_device(cls_pairer* p, const void* d_a, const void* d_b, uint32_t stride, uint32_t n, uint32_t flags,
+                            void* d_out, void* d_how, void* hip_stream);
+/* Host buffers through the same kernel; synchronous.  `how` may be NULL. */
+int cls_pair_records(cls_pairer* p, const cls_placement* a, const cls_placement* b, uint32_t stride, uint32_t n, uint32_t flags,
+                     cls_placement* out, uint8_t* how);
+/* Host only, sequential, no device: the statement of the rules above and the yardstick of the kernel.  The tree as
+ * cls_tally_host takes it.  `how` may be NULL; `totals` (may be NULL) is ADDED to. */
+int cls_pair_host(const cls_node* nodes, uint32_t n_nodes, const cls_placement* a, const cls_placement* b, uint32_t stride,
+                  uint64_t n, uint32_t flags, cls_placement* out, uint8_t* how, cls_pair_totals* totals);
+
+/* Mate names.  The name of a header is its bytes up to the first space or tab; if that ends in "/1" or "/2", those two
+ * bytes are dropped.  A pair agrees iff the two names are byte-equal (the suffixes are not checked against the mate's
+ * position).  Header of mate m of pair i: bytes [off_m[i * stride], off_m[i * stride + 1]) of headers_m -- two header
+ * sets with stride 1, or one interleaved set with stride 2 and off2 = off1 + 1.  *n_bad = disagreeing pairs,
+ * *first_bad = the lowest disagreeing index (UINT64_MAX if none). */
+int cls_pair_names_host(const char* headers1, const uint64_t* off1, const char* headers2, const uint64_t* off2, uint32_t stride,
+                        uint64_t n, uint64_t* n_bad, uint64_t* first_bad);
+/* Its device twin: the arrays are in the HBM of the current device (cls_fasta_dev of the FASTQ stage); synchronises
+ * `hip_stream` to hand the two results back. */
+int cls_pair_names_device(const void* d_headers1, const void* d_off1, const void* d_headers2, const void* d_off2, uint32_t stride,
+                          uint32_t n, uint64_t* n_bad, uint64_t* first_bad, void* hip_stream);
+
+/* Paired FASTQ text -> one record per pair.  `text2` == NULL: `text1` is interleaved (records 2 i and 2 i + 1 are the
+ * mates of pair i).  Both texts go to the device once; the FASTQ stage runs on each (one scan for interleaved input);
+ * all 2 n reads are placed as ONE cls_place_batch_device batch (R1's bases then R2's, or the interleaved batch as it
+ * is); then the name check and the pairing kernel.  Only mate 1's headers (`fa`: n = pairs, truncated, headers,
+ * header_off; cls_fasta_free() it), P (`*records`) and `*how` (may be NULL; free() both) return to the host.  The
+ * classes are added to the totals of `p`.  CLS_E_BAD_PAIRS: the two texts hold different numbers of records, an odd
+ * interleaved count, more than 2^31 - 1 pairs, or a pair whose names disagree (the message carries the lowest such pair
+ * index and both names). */
+int cls_place_fastq_pairs_text(cls_db* db, cls_pairer* p, const char* text1, size_t len1, const char* text2, size_t len2,
+                               const cls_params* params, const cls_fastq_opts* opts, uint32_t flags, cls_fasta* fa,
+                               cls_placement** records, uint8_t** how);
+/* The same pipeline into a tally: P is added to `tally` on the device, nothing per read returns.  *n_pairs,
+ * *truncated may be NULL. */
+int cls_tally_fastq_pairs_text(cls_db* db, cls_pairer* p, cls_tally* tally, const char* text1, size_t len1, const char* text2,
+                               size_t len2, const cls_params* params, const cls_fastq_opts* opts, uint32_t flags,
+                               uint32_t* n_pairs, uint32_t* truncated);
 
 /* Experiment knobs (grid sizes, locality-key definition, kernel family; none changes a result; names in
  * csrc/cls_tuning.h are the CLS_* variables in lower case without the prefix, e.g. "no_order").  Process-global,
