@@ -267,5 +267,9 @@ PAIR_CONSERVATIVE, PAIR_REQUIRE_BOTH = 1, 2
 E_BAD_PAIRS = -8
 PAIR_TOTALS_DTYPE = np.dtype([("n_pairs", "<u8"), ("how_count", "<u8", (8,))])
 assert PAIR_TOTALS_DTYPE.itemsize == 72
+# read extraction (cls_extract_totals, CLS_SELECT_*)
+SELECT_UNPLACED = 1
+EXTRACT_TOTALS_DTYPE = np.dtype([("n_records", "<u8"), ("n_selected", "<u8"), ("n_selected_unplaced", "<u8"), ("bytes_out", "<u8")])
+assert EXTRACT_TOTALS_DTYPE.itemsize == 32
 assert NODE_DTYPE.itemsize == 32 and PLACEMENT_DTYPE.itemsize == 24 and STATS_DTYPE.itemsize == 24
 assert TALLY_ROW_DTYPE.itemsize == 64 and TALLY_TOTALS_DTYPE.itemsize == 120

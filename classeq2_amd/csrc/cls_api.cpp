@@ -16,6 +16,7 @@
 
 #include "cls_db.h"
 #include "cls_device.h"
+#include "cls_extract.h"
 #include "cls_kernels.h"
 #include "cls_pair.h"
 #include "cls_place.h"
@@ -873,6 +874,22 @@ extern "C" int cls_place_batch_group(cls_db_group* g, const char* bases, const u
 
 // ---- clade tally (include/cls_place.h; kernels in cls_tally.hip) ----------------------------------------------------
 
+// id -> pre-order index of the handle's clades as the kernels probe it (IdSlot, tally_hash): the tally, the pairer and
+// the selector each upload a copy.
+static std::vector<cls::IdSlot> id_table(const cls_db* db) {
+    const uint32_t n = (uint32_t)db->tree_rows.size();
+    uint32_t cap = 16;
+    while (cap < 2 * n) cap *= 2;
+    std::vector<cls::IdSlot> table(cap, cls::IdSlot{0, cls::TALLY_NO_PRE, 0});
+    for (const auto& r : db->tree_rows) {
+        uint32_t h = (uint32_t)cls::tally_hash(r.id) & (cap - 1);
+        while (table[h].pre != cls::TALLY_NO_PRE) h = (h + 1) & (cap - 1);
+        table[h].id = r.id;
+        table[h].pre = r.pre;
+    }
+    return table;
+}
+
 struct cls_tally {
     cls_db* db = nullptr;
     cls::TallyDev dev{};
@@ -928,17 +945,10 @@ extern "C" int cls_tally_create(cls_db* db, cls_tally** out) {
     try {
         const uint32_t n = (uint32_t)db->tree_rows.size();
         if (n == 0 || n >= cls::TALLY_MAX_NODES) return fail(CLS_E_INVALID_ARG, "cls_tally_create: the tree has too many clades for a tally");
-        uint32_t cap = 16;
-        while (cap < 2 * n) cap *= 2;
-        std::vector<cls::IdSlot> table(cap, cls::IdSlot{0, cls::TALLY_NO_PRE, 0});
+        const std::vector<cls::IdSlot> table = id_table(db);
+        const uint32_t cap = (uint32_t)table.size();
         std::vector<uint32_t> size_by_pre(n);
-        for (const auto& r : db->tree_rows) {
-            uint32_t h = (uint32_t)cls::tally_hash(r.id) & (cap - 1);
-            while (table[h].pre != cls::TALLY_NO_PRE) h = (h + 1) & (cap - 1);
-            table[h].id = r.id;
-            table[h].pre = r.pre;
-            size_by_pre[r.pre] = r.size;
-        }
+        for (const auto& r : db->tree_rows) size_by_pre[r.pre] = r.size;
         DeviceScope ds;
         CLS_HIP(ds.enter(db->device));
         t = new cls_tally();
@@ -1187,6 +1197,353 @@ extern "C" int cls_tally_host(const cls_node* nodes, uint32_t n_nodes, const cls
     }
 }
 
+// ---- read extraction (include/cls_place.h; kernels in cls_extract.hip) ------------------------------------------------
+
+struct cls_selector {
+    cls_db* db = nullptr;
+    cls::SelectDev dev{};
+    void* d_table = nullptr;      // a copy of the id table (id_table)
+    void* d_sel = nullptr;        // sel_by_pre[n]
+    hipStream_t stream = nullptr; // upload and the host-record calls
+    std::mutex mu;                // (one host-record call at a time on `stream`)
+};
+
+// The two lists as (id, 1: include / 2: exclude), ascending by id; refuses what cls_place.h refuses.
+static int selector_lists(const char* who, const uint64_t* include, uint32_t n_include, const uint64_t* exclude, uint32_t n_exclude, uint32_t flags,
+                          std::vector<std::pair<uint64_t, uint8_t>>& listed) {
+    if ((n_include && !include) || (n_exclude && !exclude)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": null list");
+    if (flags & ~CLS_SELECT_UNPLACED) return fail(CLS_E_INVALID_ARG, std::string(who) + ": unknown flag bit");
+    listed.clear();
+    listed.reserve((size_t)n_include + n_exclude);
+    for (uint32_t i = 0; i < n_include; ++i) listed.push_back({include[i], (uint8_t)1});
+    for (uint32_t i = 0; i < n_exclude; ++i) listed.push_back({exclude[i], (uint8_t)2});
+    std::sort(listed.begin(), listed.end());
+    for (size_t i = 1; i < listed.size(); ++i)
+        if (listed[i].first == listed[i - 1].first)
+            return fail(CLS_E_INVALID_ARG, std::string(who) + ": clade id " + std::to_string(listed[i].first) +
+                                               (listed[i].second == listed[i - 1].second ? " is listed twice" : " is listed as include and as exclude"));
+    return CLS_OK;
+}
+
+extern "C" void cls_selector_destroy(cls_selector* s) {
+    if (!s) return;
+    DeviceScope ds;
+    (void)ds.enter(s->db->device);
+    if (s->stream) { (void)hipStreamSynchronize(s->stream); (void)hipStreamDestroy(s->stream); }
+    for (void* x : {s->d_table, s->d_sel}) if (x) (void)hipFree(x);
+    delete s;
+}
+
+extern "C" int cls_selector_create(cls_db* db, const uint64_t* include, uint32_t n_include, const uint64_t* exclude, uint32_t n_exclude,
+                                   uint32_t flags, cls_selector** out) {
+    if (!db || !out) return fail(CLS_E_INVALID_ARG, "cls_selector_create: null argument");
+    *out = nullptr;
+    cls_selector* s = nullptr;
+    try {
+        const uint32_t n = (uint32_t)db->tree_rows.size();
+        if (n == 0 || n >= cls::TALLY_MAX_NODES) return fail(CLS_E_INVALID_ARG, "cls_selector_create: the tree has too many clades for a selector");
+        std::vector<std::pair<uint64_t, uint8_t>> listed;
+        if (int rc = selector_lists("cls_selector_create", include, n_include, exclude, n_exclude, flags, listed)) return rc;
+        // the listed clades' pre-order intervals, painted ancestors first: the innermost listed clade decides
+        std::vector<std::pair<uint64_t, uint32_t>> by_id(n);
+        for (uint32_t r = 0; r < n; ++r) by_id[r] = {db->tree_rows[r].id, r};
+        std::sort(by_id.begin(), by_id.end());
+        struct Span { uint32_t pre, size; uint8_t kind; };
+        std::vector<Span> spans;
+        spans.reserve(listed.size());
+        for (const auto& x : listed) {
+            auto it = std::lower_bound(by_id.begin(), by_id.end(), std::make_pair(x.first, (uint32_t)0));
+            if (it == by_id.end() || it->first != x.first)
+                return fail(CLS_E_INVALID_ARG, "cls_selector_create: " + std::to_string(x.first) + " is no clade id of the tree");
+            const auto& tr = db->tree_rows[it->second];
+            spans.push_back({tr.pre, tr.size, x.second});
+        }
+        std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.pre < b.pre; });
+        std::vector<uint8_t> sel_by_pre(n, 0);
+        for (const Span& x : spans) std::fill(sel_by_pre.begin() + x.pre, sel_by_pre.begin() + x.pre + x.size, (uint8_t)(x.kind == 1 ? 1 : 0));
+        const std::vector<cls::IdSlot> table = id_table(db);
+        DeviceScope ds;
+        CLS_HIP(ds.enter(db->device));
+        s = new cls_selector();
+        s->db = db;
+        hipError_t e;
+        if ((e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)) != hipSuccess ||
+            (e = hipMalloc(&s->d_table, table.size() * sizeof(cls::IdSlot))) != hipSuccess ||
+            (e = hipMalloc(&s->d_sel, n)) != hipSuccess ||
+            (e = hipMemcpyAsync(s->d_table, table.data(), table.size() * sizeof(cls::IdSlot), hipMemcpyHostToDevice, s->stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(s->d_sel, sel_by_pre.data(), n, hipMemcpyHostToDevice, s->stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(s->stream)) != hipSuccess) {
+            cls_selector_destroy(s);
+            return fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string("cls_selector_create: ") + hipGetErrorString(e));
+        }
+        s->dev.table = (const cls::IdSlot*)s->d_table;
+        s->dev.table_mask = (uint32_t)table.size() - 1;
+        s->dev.n_nodes = n;
+        s->dev.sel_by_pre = (const uint8_t*)s->d_sel;
+        s->dev.unplaced = (flags & CLS_SELECT_UNPLACED) ? 1u : 0u;
+        *out = s;
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        cls_selector_destroy(s);
+        return fail(CLS_E_NOMEM, "cls_selector_create: out of host memory");
+    } catch (...) {
+        cls_selector_destroy(s);
+        return fail(CLS_E_INTERNAL, "cls_selector_create: unknown exception");
+    }
+}
+
+// The launch on `stream` (the handle's device is current).  `d_n_unplaced`: see launch_select_records.
+static int select_on(cls_selector* s, const void* d_records, uint32_t n, void* d_sel, unsigned long long* d_n_unplaced, hipStream_t stream) {
+    if (((uintptr_t)d_records & 7) != 0) return fail(CLS_E_INVALID_ARG, "cls_select_records_device: records must be 8-byte aligned");
+    CLS_HIP(cls::launch_select_records(s->dev, d_records, n, (uint8_t*)d_sel, d_n_unplaced, stream));
+    return CLS_OK;
+}
+
+extern "C" int cls_select_records_device(cls_selector* s, const void* d_records, uint32_t n, void* d_sel, void* hip_stream) {
+    if (!s) return fail(CLS_E_INVALID_ARG, "cls_select_records_device: null handle");
+    if (n == 0) return CLS_OK;
+    if (!d_records || !d_sel) return fail(CLS_E_INVALID_ARG, "cls_select_records_device: null buffer");
+    DeviceScope ds;
+    CLS_HIP(ds.enter(s->db->device));
+    return select_on(s, d_records, n, d_sel, nullptr, (hipStream_t)hip_stream);
+}
+
+extern "C" int cls_select_records(cls_selector* s, const cls_placement* records, uint32_t n, uint8_t* sel) {
+    if (!s) return fail(CLS_E_INVALID_ARG, "cls_select_records: null handle");
+    if (n == 0) return CLS_OK;
+    if (!records || !sel) return fail(CLS_E_INVALID_ARG, "cls_select_records: null buffer");
+    DeviceScope ds;
+    CLS_HIP(ds.enter(s->db->device));
+    const size_t rec_bytes = (size_t)n * sizeof(cls_placement);
+    char* d = nullptr;  // records | sel
+    hipError_t e = hipMalloc((void**)&d, rec_bytes + n);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string("cls_select_records: ") + hipGetErrorString(e));
+    int rc = CLS_OK;
+    {
+        std::lock_guard<std::mutex> g(s->mu);
+        if ((e = hipMemcpyAsync(d, records, rec_bytes, hipMemcpyHostToDevice, s->stream)) != hipSuccess)
+            rc = fail(CLS_E_HIP, std::string("cls_select_records: ") + hipGetErrorString(e));
+        else rc = select_on(s, d, n, d + rec_bytes, nullptr, s->stream);
+        if (rc == CLS_OK && (e = hipMemcpyAsync(sel, d + rec_bytes, n, hipMemcpyDeviceToHost, s->stream)) != hipSuccess)
+            rc = fail(CLS_E_HIP, std::string("cls_select_records: ") + hipGetErrorString(e));
+        e = hipStreamSynchronize(s->stream);  // synchronous; the staging copy is freed behind the kernel
+        if (rc == CLS_OK && e != hipSuccess) rc = fail(CLS_E_HIP, std::string("cls_select_records: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(d);
+    return rc;
+}
+
+// The selection rule as it is written in cls_place.h, one record after the other: a sorted id -> row list, parent rows
+// from the child ranges, and a walk from the record's clade towards the root until a listed clade is met.
+extern "C" int cls_select_host(const cls_node* nodes, uint32_t n_nodes, const uint64_t* include, uint32_t n_include, const uint64_t* exclude,
+                               uint32_t n_exclude, uint32_t flags, const cls_placement* records, uint64_t n, uint8_t* sel) {
+    if (!nodes || n_nodes == 0 || (n && (!records || !sel))) return fail(CLS_E_INVALID_ARG, "cls_select_host: null argument");
+    try {
+        std::vector<std::pair<uint64_t, uint8_t>> listed;
+        if (int rc = selector_lists("cls_select_host", include, n_include, exclude, n_exclude, flags, listed)) return rc;
+        constexpr uint32_t NONE = UINT32_MAX;
+        std::vector<uint32_t> parent_row(n_nodes, NONE);
+        std::vector<std::pair<uint64_t, uint32_t>> by_id(n_nodes);
+        for (uint32_t r = 0; r < n_nodes; ++r) {
+            by_id[r] = {nodes[r].id, r};
+            if (nodes[r].n_children == 0) continue;
+            if ((uint64_t)nodes[r].first_child + nodes[r].n_children > n_nodes || nodes[r].first_child == 0)
+                return fail(CLS_E_BAD_TREE, "cls_select_host: child rows out of range");
+            for (uint32_t c = nodes[r].first_child; c < nodes[r].first_child + nodes[r].n_children; ++c) {
+                if (parent_row[c] != NONE) return fail(CLS_E_BAD_TREE, "cls_select_host: row is the child of two parents (not a tree)");
+                parent_row[c] = r;
+            }
+        }
+        if (parent_row[0] != NONE) return fail(CLS_E_BAD_TREE, "cls_select_host: the root has a parent");
+        for (uint32_t r = 1; r < n_nodes; ++r)
+            if (parent_row[r] == NONE) return fail(CLS_E_BAD_TREE, "cls_select_host: rows unreachable from the root");
+        std::sort(by_id.begin(), by_id.end());
+        for (uint32_t r = 1; r < n_nodes; ++r)
+            if (by_id[r].first == by_id[r - 1].first) return fail(CLS_E_BAD_TREE, "cls_select_host: duplicate clade id " + std::to_string(by_id[r].first));
+        auto row_of = [&](uint64_t id) -> uint32_t {
+            auto it = std::lower_bound(by_id.begin(), by_id.end(), std::make_pair(id, (uint32_t)0));
+            return (it == by_id.end() || it->first != id) ? NONE : it->second;
+        };
+        std::vector<uint8_t> mark(n_nodes, 0);  // 1: include, 2: exclude
+        for (const auto& x : listed) {
+            const uint32_t r = row_of(x.first);
+            if (r == NONE) return fail(CLS_E_INVALID_ARG, "cls_select_host: " + std::to_string(x.first) + " is no clade id of the tree");
+            mark[r] = x.second;
+        }
+        const bool unplaced = (flags & CLS_SELECT_UNPLACED) != 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const cls_placement& p = records[i];
+            uint32_t r = NONE;
+            if (p.status == CLS_IDENTITY_FOUND || p.status == CLS_MAX_RESOLUTION || p.status == CLS_INCONCLUSIVE) r = row_of(p.clade_id);
+            if (r == NONE) { sel[i] = unplaced ? 1 : 0; continue; }
+            while (mark[r] == 0 && parent_row[r] != NONE) r = parent_row[r];
+            sel[i] = mark[r] == 1 ? 1 : 0;
+        }
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CLS_E_NOMEM, "cls_select_host: out of host memory");
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_select_host: unknown exception");
+    }
+}
+
+extern "C" int cls_fastq_spans_device(const void* d_text, uint64_t len, uint32_t n, void* d_rec_off, void* hip_stream) {
+    if (!d_rec_off || (!d_text && len)) return fail(CLS_E_INVALID_ARG, "cls_fastq_spans_device: null argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    uint64_t* d_ls = nullptr;
+    uint64_t n_nl = 0;
+    if (int rc = cls::fastq_line_starts_device(d_text, len, &d_ls, &n_nl, stream)) return rc;
+    hipError_t e = cls::launch_fastq_spans(d_ls, n_nl, len, n, (uint64_t*)d_rec_off, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // (the line starts are freed behind the kernel)
+    if (d_ls) (void)hipFree(d_ls);
+    if (e != hipSuccess) return fail(CLS_E_HIP, std::string("cls_fastq_spans_device: ") + hipGetErrorString(e));
+    return CLS_OK;
+}
+
+static int check_extract_args(const char* who, uint32_t stride, uint64_t n_items) {
+    if (stride != 1 && stride != 2) return fail(CLS_E_INVALID_ARG, std::string(who) + ": stride must be 1 or 2");
+    if (n_items * stride > 0xFFFFFFFFull) return fail(CLS_E_INVALID_ARG, std::string(who) + ": more than 2^32 - 1 records");
+    return CLS_OK;
+}
+
+// The plan on `stream` with scratch of its own; synchronises `stream` to hand the sizes back.
+static int extract_plan_on(const char* who, const void* d_text, const void* d_rec_off, uint32_t stride, uint32_t n_items, const void* d_sel,
+                           void* d_out_off, cls_extract_totals* totals, hipStream_t stream) {
+    memset(totals, 0, sizeof *totals);
+    totals->n_records = n_items;
+    void* d_tmp = nullptr;
+    unsigned long long* d_cnt = nullptr;
+    const size_t tmp_bytes = cls::extract_scan_tmp_bytes(n_items);
+    unsigned long long cnt = 0;
+    uint64_t bytes = 0;
+    hipError_t e;
+    if ((e = hipMalloc(&d_tmp, tmp_bytes)) == hipSuccess && (e = hipMalloc((void**)&d_cnt, 8)) == hipSuccess &&
+        (e = hipMemsetAsync(d_cnt, 0, 8, stream)) == hipSuccess &&
+        (e = cls::launch_extract_plan((const uint8_t*)d_text, (const uint64_t*)d_rec_off, stride, n_items, (const uint8_t*)d_sel, (uint64_t*)d_out_off,
+                                      d_cnt, d_tmp, tmp_bytes, stream)) == hipSuccess &&
+        (e = hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, stream)) == hipSuccess &&
+        (e = hipMemcpyAsync(&bytes, (const uint64_t*)d_out_off + n_items, 8, hipMemcpyDeviceToHost, stream)) == hipSuccess)
+        e = hipStreamSynchronize(stream);
+    if (d_tmp) (void)hipFree(d_tmp);
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    totals->n_selected = cnt;
+    totals->bytes_out = bytes;
+    return CLS_OK;
+}
+
+extern "C" int cls_extract_plan_device(const void* d_text, const void* d_rec_off, uint32_t stride, uint32_t n_items, const void* d_sel,
+                                       void* d_out_off, cls_extract_totals* totals, void* hip_stream) {
+    if (!d_out_off || !totals || (n_items && (!d_rec_off || !d_sel))) return fail(CLS_E_INVALID_ARG, "cls_extract_plan_device: null argument");
+    if (int rc = check_extract_args("cls_extract_plan_device", stride, n_items)) return rc;
+    if ((uintptr_t)d_out_off & 7 || (uintptr_t)d_rec_off & 7) return fail(CLS_E_INVALID_ARG, "cls_extract_plan_device: offsets must be 8-byte aligned");
+    return extract_plan_on("cls_extract_plan_device", d_text, d_rec_off, stride, n_items, d_sel, d_out_off, totals, (hipStream_t)hip_stream);
+}
+
+extern "C" int cls_extract_gather_device(const void* d_text, const void* d_rec_off, uint32_t stride, uint32_t n_items, const void* d_sel,
+                                         const void* d_out_off, void* d_out, void* hip_stream) {
+    if (int rc = check_extract_args("cls_extract_gather_device", stride, n_items)) return rc;
+    if (n_items == 0) return CLS_OK;
+    if (!d_rec_off || !d_sel || !d_out_off || !d_out) return fail(CLS_E_INVALID_ARG, "cls_extract_gather_device: null argument");
+    if ((uintptr_t)d_out_off & 7 || (uintptr_t)d_rec_off & 7) return fail(CLS_E_INVALID_ARG, "cls_extract_gather_device: offsets must be 8-byte aligned");
+    CLS_HIP(cls::launch_extract_gather((const uint8_t*)d_text, (const uint64_t*)d_rec_off, stride, n_items, (const uint8_t*)d_sel,
+                                       (const uint64_t*)d_out_off, (uint8_t*)d_out, (hipStream_t)hip_stream));
+    return CLS_OK;
+}
+
+// Record text and output as they are written in cls_place.h, one line and one item after the other.
+extern "C" int cls_extract_host(const char* text, size_t len, uint32_t stride, const uint8_t* sel, uint64_t n_items, char** out, size_t* out_len,
+                                cls_extract_totals* totals) {
+    if (!out || !out_len || !totals || (!text && len) || (n_items && !sel)) return fail(CLS_E_INVALID_ARG, "cls_extract_host: null argument");
+    *out = nullptr;
+    *out_len = 0;
+    if (int rc = check_extract_args("cls_extract_host", stride, n_items)) return rc;
+    try {
+        const uint64_t n = n_items * stride;
+        std::vector<uint64_t> rec_off(n + 1, (uint64_t)len);  // (a line that does not start inside the text: `len`)
+        uint64_t pos = 0;                                      // the start of line `line`
+        for (uint64_t line = 0; line <= 4 * n && pos < len; ++line) {
+            if (line % 4 == 0) rec_off[line / 4] = pos;
+            const char* nl = (const char*)memchr(text + pos, '\n', len - pos);
+            pos = nl ? (uint64_t)(nl - text) + 1 : (uint64_t)len;
+        }
+        memset(totals, 0, sizeof *totals);
+        totals->n_records = n_items;
+        uint64_t bytes = 0;
+        for (uint64_t i = 0; i < n_items; ++i) {
+            if (!sel[i]) continue;
+            totals->n_selected++;
+            const uint64_t a = rec_off[i * stride], b = rec_off[(i + 1) * stride];
+            if (b > a) bytes += (b - a) + (text[b - 1] != '\n' ? 1 : 0);
+        }
+        char* o = (char*)malloc(bytes + 1);
+        if (!o) return fail(CLS_E_NOMEM, "cls_extract_host: out of host memory");
+        uint64_t w = 0;
+        for (uint64_t i = 0; i < n_items; ++i) {
+            if (!sel[i]) continue;
+            const uint64_t a = rec_off[i * stride], b = rec_off[(i + 1) * stride];
+            if (b <= a) continue;
+            memcpy(o + w, text + a, b - a);
+            w += b - a;
+            if (text[b - 1] != '\n') o[w++] = '\n';
+        }
+        o[w] = 0;
+        totals->bytes_out = bytes;
+        *out = o;
+        *out_len = (size_t)bytes;
+        return CLS_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(CLS_E_NOMEM, "cls_extract_host: out of host memory");
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_extract_host: unknown exception");
+    }
+}
+
+// What the extract entries hang on place_text / pairs_text: the text stays on the device until the gather.
+struct ExtractHook {
+    cls_selector* s;
+    char** out1;
+    size_t* out1_len;
+    char** out2;                 // pairs with two texts: R2's records
+    size_t* out2_len;
+    cls_extract_totals* totals;
+};
+
+// Spans from the FASTQ stage's line starts, plan, gather, D2H of the selected bytes: one text of a fused entry.
+// *out is malloc'ed on success only.  totals: n_selected is set, bytes_out is ADDED to.
+static int extract_stage(const char* who, const void* d_text, uint64_t len, const uint64_t* d_ls, uint64_t n_nl, uint32_t n_records,
+                         uint32_t stride, uint32_t n_items, const void* d_sel, hipStream_t stream, char** out, size_t* out_len,
+                         cls_extract_totals* totals) {
+    void *d_rec_off = nullptr, *d_out_off = nullptr, *d_bytes = nullptr;
+    char* h = nullptr;
+    auto done = [&](int rc) {
+        for (void* x : {d_rec_off, d_out_off, d_bytes}) if (x) (void)hipFree(x);
+        if (rc != CLS_OK) free(h);
+        return rc;
+    };
+    auto hip_fail = [&](hipError_t e) { return done(fail(e == hipErrorOutOfMemory ? CLS_E_NOMEM : CLS_E_HIP, std::string(who) + ": " + hipGetErrorString(e))); };
+    hipError_t e;
+    if ((e = hipMalloc(&d_rec_off, ((size_t)n_records + 1) * 8)) != hipSuccess || (e = hipMalloc(&d_out_off, ((size_t)n_items + 1) * 8)) != hipSuccess ||
+        (e = cls::launch_fastq_spans(d_ls, n_nl, len, n_records, (uint64_t*)d_rec_off, stream)) != hipSuccess)
+        return hip_fail(e);
+    cls_extract_totals t;
+    if (int rc = extract_plan_on(who, d_text, d_rec_off, stride, n_items, d_sel, d_out_off, &t, stream)) return done(rc);
+    h = (char*)malloc(t.bytes_out + 1);
+    if (!h) return done(fail(CLS_E_NOMEM, std::string(who) + ": out of host memory"));
+    if ((e = hipMalloc(&d_bytes, t.bytes_out + 16)) != hipSuccess ||
+        (e = cls::launch_extract_gather((const uint8_t*)d_text, (const uint64_t*)d_rec_off, stride, n_items, (const uint8_t*)d_sel,
+                                        (const uint64_t*)d_out_off, (uint8_t*)d_bytes, stream)) != hipSuccess ||
+        (t.bytes_out && (e = hipMemcpyAsync(h, d_bytes, t.bytes_out, hipMemcpyDeviceToHost, stream)) != hipSuccess) ||
+        (e = hipStreamSynchronize(stream)) != hipSuccess)
+        return hip_fail(e);
+    h[t.bytes_out] = 0;
+    totals->n_selected = t.n_selected;
+    totals->bytes_out += t.bytes_out;
+    *out = h;
+    *out_len = (size_t)t.bytes_out;
+    return done(CLS_OK);
+}
+
 // Query text -> records, all on the device: H2D of the file bytes, `scan` (the device FASTA or FASTQ stage),
 // placement straight from the scanned bases, D2H of the 24-byte records and of the headers (the output stage needs
 // those on the host).  `fa->bases` / `fa->base_off` come back NULL: the bases never leave the device.  `who` names the
@@ -1194,10 +1551,14 @@ extern "C" int cls_tally_host(const cls_node* nodes, uint32_t n_nodes, const cls
 using ScanText = int (*)(const void* d_text, uint64_t len, const void* opts, cls_fasta_dev* out, hipStream_t stream);
 // With `tally` (the cls_tally_*_text entries) the records are added to it on the device instead: `fa` only carries n and
 // truncated, `records` is NULL, and neither the headers, their offsets nor the records are copied back.
+// With `ex` (cls_extract_fastq_text; FASTQ only, `scan` is not used) nothing per read is copied back either: the text
+// stays on the device behind the scan, every chunk's records go through the selector, and the selected records' bytes
+// are gathered from the text and returned.
 static int place_text(const char* who, cls_db* db, const char* text, size_t len, const cls_params* params, ScanText scan,
-                      const void* scan_opts, cls_fasta* fa, cls_placement** records, cls_tally* tally = nullptr) {
-    if (!db || !fa || (!records && !tally) || (!text && len)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": null argument");
+                      const void* scan_opts, cls_fasta* fa, cls_placement** records, cls_tally* tally = nullptr, const ExtractHook* ex = nullptr) {
+    if (!db || !fa || (!records && !tally && !ex) || (!text && len)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": null argument");
     if (tally && tally->db != db) return fail(CLS_E_INVALID_ARG, std::string(who) + ": the tally belongs to another handle");
+    if (ex && ex->s->db != db) return fail(CLS_E_INVALID_ARG, std::string(who) + ": the selector belongs to another handle");
     memset(fa, 0, sizeof *fa);
     if (records) *records = nullptr;
     int prev = 0;
@@ -1205,6 +1566,9 @@ static int place_text(const char* who, cls_db* db, const char* text, size_t len,
     CLS_HIP(hipSetDevice(db->device));
     hipStream_t stream = nullptr;
     void *d_text = nullptr, *d_out = nullptr;
+    uint64_t* d_ls = nullptr;      // `ex`: the scan's line starts
+    uint64_t n_nl = 0;
+    char* d_selbuf = nullptr;      // `ex`: the selected-unplaced counter (8 bytes) | one byte per record
     cls_fasta_dev dv;
     memset(&dv, 0, sizeof dv);
     cls_placement* recs = nullptr;
@@ -1212,6 +1576,8 @@ static int place_text(const char* who, cls_db* db, const char* text, size_t len,
     auto cleanup = [&]() {
         if (d_text) (void)hipFree(d_text);
         if (d_out) (void)hipFree(d_out);
+        if (d_ls) (void)hipFree(d_ls);
+        if (d_selbuf) (void)hipFree(d_selbuf);
         cls_fasta_dev_free(&dv);
         if (stream) (void)hipStreamDestroy(stream);
         (void)hipSetDevice(prev);
@@ -1226,15 +1592,22 @@ static int place_text(const char* who, cls_db* db, const char* text, size_t len,
         CLS_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         CLS_TRY(hipMalloc(&d_text, len ? len : 16));
         if (len) CLS_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, stream));
-        int rc = scan(d_text, len, scan_opts, &dv, stream);
+        int rc = ex ? cls::fastq_scan_device_keep(d_text, len, (const cls_fastq_opts*)scan_opts, &dv, stream, &d_ls, &n_nl)
+                    : scan(d_text, len, scan_opts, &dv, stream);
         if (rc != CLS_OK) { cleanup(); return rc; }
-        (void)hipFree(d_text);
-        d_text = nullptr;
+        if (!ex) {  // (an extraction gathers from the text at the end)
+            (void)hipFree(d_text);
+            d_text = nullptr;
+        }
         const uint32_t n = dv.n;
         fa->n = n;
         fa->truncated = dv.truncated;
         std::vector<uint64_t> boff((size_t)n + 1);
-        if (!tally) {
+        if (ex) {
+            CLS_TRY(hipMalloc((void**)&d_selbuf, 8 + (size_t)n + 8));
+            CLS_TRY(hipMemsetAsync(d_selbuf, 0, 8, stream));
+        }
+        if (!tally && !ex) {
             fa->headers = (char*)malloc(dv.n_header_bytes + 1);
             fa->header_off = (uint64_t*)malloc(((size_t)n + 1) * 8);
             recs = (cls_placement*)malloc(((size_t)n + 1) * sizeof(cls_placement));
@@ -1261,8 +1634,22 @@ static int place_text(const char* who, cls_db* db, const char* text, size_t len,
             if (tally) {
                 rc = tally_add_on(tally, d_out, cnt, stream, false);  // (in stream order behind the placement; waited for below)
                 if (rc != CLS_OK) { cleanup(); return rc; }
-            } else CLS_TRY(hipMemcpyAsync(recs + first, d_out, (size_t)cnt * sizeof(cls_placement), hipMemcpyDeviceToHost, stream));
+            } else if (!ex) CLS_TRY(hipMemcpyAsync(recs + first, d_out, (size_t)cnt * sizeof(cls_placement), hipMemcpyDeviceToHost, stream));
+            if (ex) {
+                rc = select_on(ex->s, d_out, cnt, d_selbuf + 8 + first, (unsigned long long*)d_selbuf, stream);
+                if (rc != CLS_OK) { cleanup(); return rc; }
+            }
             CLS_TRY(hipStreamSynchronize(stream));
+        }
+        if (ex) {
+            unsigned long long n_unplaced = 0;
+            CLS_TRY(hipMemcpyAsync(&n_unplaced, d_selbuf, 8, hipMemcpyDeviceToHost, stream));
+            CLS_TRY(hipStreamSynchronize(stream));
+            memset(ex->totals, 0, sizeof *ex->totals);
+            ex->totals->n_records = n;
+            ex->totals->n_selected_unplaced = n_unplaced;
+            rc = extract_stage(who, d_text, len, d_ls, n_nl, n, 1, n, d_selbuf + 8, stream, ex->out1, ex->out1_len, ex->totals);
+            if (rc != CLS_OK) { cleanup(); return rc; }
         }
         if (records) *records = recs;
         ok = true;
@@ -1357,19 +1744,14 @@ extern "C" int cls_pairer_create(cls_db* db, cls_pairer** out) {
     try {
         const uint32_t n = (uint32_t)db->tree_rows.size();
         if (n == 0 || n >= cls::TALLY_MAX_NODES) return fail(CLS_E_INVALID_ARG, "cls_pairer_create: the tree has too many clades for a pairer");
-        uint32_t cap = 16;
-        while (cap < 2 * n) cap *= 2;
-        std::vector<cls::IdSlot> table(cap, cls::IdSlot{0, cls::TALLY_NO_PRE, 0});
+        const std::vector<cls::IdSlot> table = id_table(db);
+        const uint32_t cap = (uint32_t)table.size();
         std::vector<uint32_t> tree(3 * (size_t)n);  // size | parent | depth, by pre
         std::vector<uint64_t> id_by_pre(n);
         uint32_t* size_by_pre = tree.data();
         uint32_t* parent_by_pre = tree.data() + n;
         uint32_t* depth_by_pre = tree.data() + 2 * (size_t)n;
         for (const auto& r : db->tree_rows) {
-            uint32_t h = (uint32_t)cls::tally_hash(r.id) & (cap - 1);
-            while (table[h].pre != cls::TALLY_NO_PRE) h = (h + 1) & (cap - 1);
-            table[h].id = r.id;
-            table[h].pre = r.pre;
             size_by_pre[r.pre] = r.size;
             id_by_pre[r.pre] = r.id;
         }
@@ -1652,11 +2034,14 @@ extern "C" int cls_pair_names_device(const void* d_headers1, const void* d_off1,
 
 // Paired FASTQ text -> P (and `how`), all on the device; see cls_place_fastq_pairs_text in cls_place.h.  With `tally`
 // P is added to it on the device instead and nothing per read is copied back (`fa` carries n and truncated only).
+// With `ex` (cls_extract_fastq_pairs_text) nothing per pair is copied back: both texts stay on the device behind their
+// scans, P goes through the selector, and the selected pairs' bytes are gathered from each text.
 static int pairs_text(const char* who, cls_db* db, cls_pairer* p, cls_tally* tally, const char* text1, size_t len1, const char* text2,
                       size_t len2, const cls_params* params, const cls_fastq_opts* opts, uint32_t flags, cls_fasta* fa,
-                      cls_placement** records, uint8_t** how) {
-    if (!db || !p || !fa || (!records && !tally) || (!text1 && len1) || (!text2 && len2)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": null argument");
+                      cls_placement** records, uint8_t** how, const ExtractHook* ex = nullptr) {
+    if (!db || !p || !fa || (!records && !tally && !ex) || (!text1 && len1) || (!text2 && len2)) return fail(CLS_E_INVALID_ARG, std::string(who) + ": null argument");
     if (p->db != db) return fail(CLS_E_INVALID_ARG, std::string(who) + ": the pairer belongs to another handle");
+    if (ex && ex->s->db != db) return fail(CLS_E_INVALID_ARG, std::string(who) + ": the selector belongs to another handle");
     if (tally && tally->db != db) return fail(CLS_E_INVALID_ARG, std::string(who) + ": the tally belongs to another handle");
     const uint32_t stride = text2 ? 1u : 2u;
     if (int rc = check_pair_flags(who, stride, flags)) return rc;
@@ -1668,6 +2053,10 @@ static int pairs_text(const char* who, cls_db* db, cls_pairer* p, cls_tally* tal
     CLS_HIP(hipSetDevice(db->device));
     hipStream_t stream = nullptr;
     void *d_text = nullptr, *d_bases = nullptr, *d_off = nullptr, *d_recs = nullptr, *d_P = nullptr, *d_how = nullptr, *d_hdr = nullptr, *d_new_off = nullptr;
+    void* d_kept[2] = {nullptr, nullptr};   // `ex`: the texts, kept for the gather
+    uint64_t* d_ls[2] = {nullptr, nullptr}; // `ex`: their line starts
+    uint64_t n_nl[2] = {0, 0};
+    char* d_selbuf = nullptr;               // `ex`: the selected-unplaced counter (8 bytes) | one byte per pair
     cls_fasta_dev dv1, dv2;
     memset(&dv1, 0, sizeof dv1);
     memset(&dv2, 0, sizeof dv2);
@@ -1675,7 +2064,8 @@ static int pairs_text(const char* who, cls_db* db, cls_pairer* p, cls_tally* tal
     uint8_t* h_how = nullptr;
     bool ok = false;
     auto cleanup = [&]() {
-        for (void* x : {d_text, d_bases, d_off, d_recs, d_P, d_how, d_hdr, d_new_off}) if (x) (void)hipFree(x);
+        for (void* x : {d_text, d_bases, d_off, d_recs, d_P, d_how, d_hdr, d_new_off, d_kept[0], d_kept[1], (void*)d_ls[0], (void*)d_ls[1], (void*)d_selbuf})
+            if (x) (void)hipFree(x);
         cls_fasta_dev_free(&dv1);
         cls_fasta_dev_free(&dv2);
         if (stream) (void)hipStreamDestroy(stream);
@@ -1696,9 +2086,11 @@ static int pairs_text(const char* who, cls_db* db, cls_pairer* p, cls_tally* tal
         for (int m = 0; m < (text2 ? 2 : 1); ++m) {
             CLS_TRY(hipMalloc(&d_text, lens[m] ? lens[m] : 16));
             if (lens[m]) CLS_TRY(hipMemcpyAsync(d_text, texts[m], lens[m], hipMemcpyHostToDevice, stream));
-            const int rc = cls_fastq_scan_device(d_text, lens[m], opts, dvs[m], stream);
+            const int rc = ex ? cls::fastq_scan_device_keep(d_text, lens[m], opts, dvs[m], stream, &d_ls[m], &n_nl[m])
+                              : cls_fastq_scan_device(d_text, lens[m], opts, dvs[m], stream);
             if (rc != CLS_OK) { cleanup(); return rc; }
-            (void)hipFree(d_text);
+            if (ex) d_kept[m] = d_text;  // (an extraction gathers from the text at the end)
+            else (void)hipFree(d_text);
             d_text = nullptr;
         }
         if (text2 && dv1.n != dv2.n) {
@@ -1785,12 +2177,20 @@ static int pairs_text(const char* who, cls_db* db, cls_pairer* p, cls_tally* tal
             rc = pair_on(p, d_a, stride == 2 ? d_a + 1 : d_a + n, stride, n, flags, d_P, d_how, stream, false);
             if (rc != CLS_OK) { cleanup(); return rc; }
         }
+        if (ex) {
+            CLS_TRY(hipMalloc((void**)&d_selbuf, 8 + (size_t)n + 8));
+            CLS_TRY(hipMemsetAsync(d_selbuf, 0, 8, stream));
+            if (n) {
+                rc = select_on(ex->s, d_P, n, d_selbuf + 8, (unsigned long long*)d_selbuf, stream);
+                if (rc != CLS_OK) { cleanup(); return rc; }
+            }
+        }
         if (tally) {
             if (n) {
                 rc = tally_add_on(tally, d_P, n, stream, false);
                 if (rc != CLS_OK) { cleanup(); return rc; }
             }
-        } else {
+        } else if (!ex) {
             fa->header_off = (uint64_t*)malloc(((size_t)n + 1) * 8);
             recs = (cls_placement*)malloc(((size_t)n + 1) * sizeof(cls_placement));
             h_how = (uint8_t*)malloc((size_t)n + 1);
@@ -1821,6 +2221,20 @@ static int pairs_text(const char* who, cls_db* db, cls_pairer* p, cls_tally* tal
             }
         }
         CLS_TRY(hipStreamSynchronize(stream));
+        if (ex) {
+            unsigned long long n_unplaced = 0;
+            CLS_TRY(hipMemcpyAsync(&n_unplaced, d_selbuf, 8, hipMemcpyDeviceToHost, stream));
+            CLS_TRY(hipStreamSynchronize(stream));
+            memset(ex->totals, 0, sizeof *ex->totals);
+            ex->totals->n_records = n;
+            ex->totals->n_selected_unplaced = n_unplaced;
+            rc = extract_stage(who, d_kept[0], len1, d_ls[0], n_nl[0], dv1.n, stride, n, d_selbuf + 8, stream, ex->out1, ex->out1_len, ex->totals);
+            if (rc == CLS_OK && text2) {
+                rc = extract_stage(who, d_kept[1], len2, d_ls[1], n_nl[1], dv2.n, 1, n, d_selbuf + 8, stream, ex->out2, ex->out2_len, ex->totals);
+                if (rc != CLS_OK) { free(*ex->out1); *ex->out1 = nullptr; *ex->out1_len = 0; }
+            }
+            if (rc != CLS_OK) { cleanup(); return rc; }
+        }
         if (records) *records = recs; else free(recs);
         if (how) *how = h_how; else free(h_how);
         ok = true;
@@ -1849,6 +2263,43 @@ extern "C" int cls_tally_fastq_pairs_text(cls_db* db, cls_pairer* p, cls_tally* 
     if (!tally) return fail(CLS_E_INVALID_ARG, "cls_tally_fastq_pairs_text: null tally");
     cls_fasta fa;
     const int rc = pairs_text("cls_tally_fastq_pairs_text", db, p, tally, text1, len1, text2, len2, params, opts, flags, &fa, nullptr, nullptr);
+    if (rc != CLS_OK) return rc;
+    if (n_pairs) *n_pairs = fa.n;
+    if (truncated) *truncated = fa.truncated;
+    return CLS_OK;
+}
+
+// ---- query text -> the selected records' text ----------------------------------------------------------------------------
+
+extern "C" int cls_extract_fastq_text(cls_db* db, cls_selector* s, cls_tally* tally, const char* text, size_t len, const cls_params* params,
+                                      const cls_fastq_opts* opts, char** out, size_t* out_len, cls_extract_totals* totals, uint32_t* n,
+                                      uint32_t* truncated) {
+    if (!s || !out || !out_len || !totals) return fail(CLS_E_INVALID_ARG, "cls_extract_fastq_text: null argument");
+    *out = nullptr;
+    *out_len = 0;
+    memset(totals, 0, sizeof *totals);
+    const ExtractHook ex{s, out, out_len, nullptr, nullptr, totals};
+    cls_fasta fa;
+    const int rc = place_text("cls_extract_fastq_text", db, text, len, params, nullptr, opts, &fa, nullptr, tally, &ex);
+    if (rc != CLS_OK) return rc;
+    if (n) *n = fa.n;
+    if (truncated) *truncated = fa.truncated;
+    return CLS_OK;
+}
+
+extern "C" int cls_extract_fastq_pairs_text(cls_db* db, cls_pairer* p, cls_selector* s, cls_tally* tally, const char* text1, size_t len1,
+                                            const char* text2, size_t len2, const cls_params* params, const cls_fastq_opts* opts, uint32_t flags,
+                                            char** out1, size_t* out1_len, char** out2, size_t* out2_len, cls_extract_totals* totals,
+                                            uint32_t* n_pairs, uint32_t* truncated) {
+    if (!s || !out1 || !out1_len || !totals || (text2 && (!out2 || !out2_len))) return fail(CLS_E_INVALID_ARG, "cls_extract_fastq_pairs_text: null argument");
+    *out1 = nullptr;
+    *out1_len = 0;
+    if (out2) *out2 = nullptr;
+    if (out2_len) *out2_len = 0;
+    memset(totals, 0, sizeof *totals);
+    const ExtractHook ex{s, out1, out1_len, out2, out2_len, totals};
+    cls_fasta fa;
+    const int rc = pairs_text("cls_extract_fastq_pairs_text", db, p, tally, text1, len1, text2, len2, params, opts, flags, &fa, nullptr, nullptr, &ex);
     if (rc != CLS_OK) return rc;
     if (n_pairs) *n_pairs = fa.n;
     if (truncated) *truncated = fa.truncated;

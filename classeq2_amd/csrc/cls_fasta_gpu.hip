@@ -30,6 +30,7 @@
 #include <climits>
 #include <string>
 
+#include "cls_extract.h"
 #include "cls_place.h"
 
 extern "C" void cls_internal_set_error(const char* msg);  // cls_api.cpp: the thread-local text behind cls_last_error()
@@ -595,9 +596,12 @@ __global__ __launch_bounds__(FQ_THREADS) void fq_scatter(const uint8_t* __restri
 
 }  // namespace
 
-extern "C" int cls_fastq_scan_device(const void* d_text, uint64_t len, const cls_fastq_opts* opts, cls_fasta_dev* out, void* hip_stream) {
+// `keep_ls` != NULL: the line starts (ls[0 .. n_nl + 1]; NULL for the empty text) are handed to the caller, who frees them.
+static int fastq_scan_impl(const void* d_text, uint64_t len, const cls_fastq_opts* opts, cls_fasta_dev* out, void* hip_stream,
+                           uint64_t** keep_ls, uint64_t* keep_n_nl) {
     if (!out || (!d_text && len)) return fa_fail(CLS_E_INVALID_ARG, "cls_fastq_scan_device: null argument");
     memset(out, 0, sizeof *out);
+    if (keep_ls) { *keep_ls = nullptr; *keep_n_nl = 0; }
     cls_fastq_opts o{};
     if (opts) {
         o = *opts;
@@ -682,6 +686,7 @@ extern "C" int cls_fastq_scan_device(const void* d_text, uint64_t len, const cls
                                nb, nh, (uint8_t*)out->d_bases, (uint8_t*)out->d_headers);
         if (hipGetLastError() != hipSuccess) { cleanup(); return fa_fail(CLS_E_HIP, "cls_fastq_scan_device: kernel launch failed"); }
         // (the temporaries are freed below; hipFree waits for the work that still reads them)
+        if (keep_ls) { *keep_ls = d_ls; *keep_n_nl = n_nl; d_ls = nullptr; }
         ok = true;
         cleanup();
         return CLS_OK;
@@ -690,6 +695,63 @@ extern "C" int cls_fastq_scan_device(const void* d_text, uint64_t len, const cls
         return fa_fail(CLS_E_INTERNAL, "cls_fastq_scan_device: unknown exception");
     }
 }
+
+extern "C" int cls_fastq_scan_device(const void* d_text, uint64_t len, const cls_fastq_opts* opts, cls_fasta_dev* out, void* hip_stream) {
+    return fastq_scan_impl(d_text, len, opts, out, hip_stream, nullptr, nullptr);
+}
+
+namespace cls {
+
+int fastq_scan_device_keep(const void* d_text, uint64_t len, const cls_fastq_opts* opts, cls_fasta_dev* out, hipStream_t stream, uint64_t** d_ls,
+                           uint64_t* n_nl) {
+    if (!d_ls || !n_nl) return fa_fail(CLS_E_INVALID_ARG, "cls_fastq_scan_device: null argument");
+    return fastq_scan_impl(d_text, len, opts, out, (void*)stream, d_ls, n_nl);
+}
+
+// Passes 1 to 3 of the FASTQ stage on their own (the stand-alone cls_fastq_spans_device).
+int fastq_line_starts_device(const void* d_text, uint64_t len, uint64_t** d_ls_out, uint64_t* n_nl_out, hipStream_t stream) {
+    if (!d_ls_out || !n_nl_out || (!d_text && len)) return fa_fail(CLS_E_INVALID_ARG, "cls_fastq_spans_device: null argument");
+    *d_ls_out = nullptr;
+    *n_nl_out = 0;
+    const uint64_t n_chunks = (len + FA_CHUNK - 1) / FA_CHUNK;
+    if (n_chunks == 0) return CLS_OK;
+    const uint8_t* text = (const uint8_t*)d_text;
+    const bool aligned = ((uintptr_t)d_text & 15) == 0;
+    uint64_t *d_cnt = nullptr, *d_ls = nullptr;
+    long long* d_lt = nullptr;
+    void* d_tmp = nullptr;
+    auto cleanup = [&]() {
+        for (void* p : {(void*)d_cnt, (void*)d_ls, (void*)d_lt, d_tmp}) if (p) (void)hipFree(p);
+        d_cnt = d_ls = nullptr; d_lt = nullptr; d_tmp = nullptr;
+    };
+    try {
+        FA_HIP(hipMalloc((void**)&d_cnt, (n_chunks + 1) * 8));
+        FA_HIP(hipMalloc((void**)&d_lt, n_chunks * 8));
+        FA_HIP(hipMemsetAsync(d_cnt + n_chunks, 0, 8, stream));
+        hipLaunchKernelGGL(fq_count_lines, dim3((unsigned)n_chunks), dim3(FQ_THREADS), 0, stream, text, len, aligned, d_cnt, d_lt);
+        size_t tmp_bytes = 0;
+        FA_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_cnt, d_cnt, (int)(n_chunks + 1), stream));
+        FA_HIP(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
+        FA_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_cnt, d_cnt, (int)(n_chunks + 1), stream));
+        uint64_t n_nl = 0;
+        FA_HIP(hipMemcpyAsync(&n_nl, d_cnt + n_chunks, 8, hipMemcpyDeviceToHost, stream));
+        FA_HIP(hipStreamSynchronize(stream));
+        FA_HIP(hipMalloc((void**)&d_ls, (n_nl + 2) * 8));
+        hipLaunchKernelGGL(fq_line_starts, dim3((unsigned)n_chunks), dim3(FQ_THREADS), 0, stream, text, len, aligned, d_cnt, n_nl, d_ls);
+        FA_HIP(hipStreamSynchronize(stream));
+        if (hipGetLastError() != hipSuccess) { cleanup(); return fa_fail(CLS_E_HIP, "cls_fastq_spans_device: kernel launch failed"); }
+        *d_ls_out = d_ls;
+        *n_nl_out = n_nl;
+        d_ls = nullptr;
+        cleanup();
+        return CLS_OK;
+    } catch (...) {
+        cleanup();
+        return fa_fail(CLS_E_INTERNAL, "cls_fastq_spans_device: unknown exception");
+    }
+}
+
+}  // namespace cls
 
 // Host text in, host records out, through the device passes (what the tests compare with cls_fastq_parse).
 extern "C" int cls_fastq_parse_gpu(const char* text, size_t len, const cls_fastq_opts* opts, int device, cls_fasta* out) {

@@ -1158,6 +1158,20 @@ extern "C" int cls_profile_sequences_group(cls_db_group* grp, const cls_tree* t,
 
 static const char* const PAIR_CLASS_NAMES[7] = {"NEITHER", "ONLY_1", "ONLY_2", "SAME", "NESTED_1", "NESTED_2", "DISCORDANT"};
 
+// The pair classes of `pairer` as tab-separated "name\tcount" lines (cls_host.h, cls_place_pairs).
+static int write_pair_summary(cls_pairer* pairer, const char* summary_path) {
+    cls_pair_totals pt;
+    const int rc = cls_pairer_totals(pairer, &pt, 0);
+    if (rc != CLS_OK) return fail(rc, cls_last_error());
+    std::string o = "n_pairs\t" + std::to_string(pt.n_pairs) + "\n";
+    for (int s = 0; s < 7; ++s) o += std::string(PAIR_CLASS_NAMES[s]) + "\t" + std::to_string(pt.how_count[s]) + "\n";
+    FILE* f = fopen(summary_path, "wb");
+    if (!f) return fail(CLS_E_INVALID_ARG, std::string("Unable to open file ") + summary_path);
+    const bool ok = fwrite(o.data(), 1, o.size(), f) == o.size();
+    if (fclose(f) != 0 || !ok) return fail(CLS_E_INTERNAL, "Error writing to file");
+    return CLS_OK;
+}
+
 extern "C" int cls_place_pairs(cls_db* db, const cls_tree* t, const char* query1, const char* query2, const char* out_file,
                                const char* report_path, const char* summary_path, const cls_params* params, const cls_fastq_opts* opts,
                                uint32_t flags, int format, int overwrite, int all_rows, uint32_t* n_pairs, double* seconds) {
@@ -1228,17 +1242,7 @@ extern "C" int cls_place_pairs(cls_db* db, const cls_tree* t, const char* query1
             }
         }
         if (report_path) if ((rc = write_report(t, rows.data(), &totals, all_rows, report_path)) != CLS_OK) return rc;
-        if (summary_path) {
-            cls_pair_totals pt;
-            rc = cls_pairer_totals(g.pairer, &pt, 0);
-            if (rc != CLS_OK) return fail(rc, cls_last_error());
-            std::string o = "n_pairs\t" + std::to_string(pt.n_pairs) + "\n";
-            for (int s = 0; s < 7; ++s) o += std::string(PAIR_CLASS_NAMES[s]) + "\t" + std::to_string(pt.how_count[s]) + "\n";
-            FILE* f = fopen(summary_path, "wb");
-            if (!f) return fail(CLS_E_INVALID_ARG, std::string("Unable to open file ") + summary_path);
-            const bool ok = fwrite(o.data(), 1, o.size(), f) == o.size();
-            if (fclose(f) != 0 || !ok) return fail(CLS_E_INTERNAL, "Error writing to file");
-        }
+        if (summary_path) if ((rc = write_pair_summary(g.pairer, summary_path)) != CLS_OK) return rc;
         if (n_pairs) *n_pairs = n;
         if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         return CLS_OK;
@@ -1246,5 +1250,119 @@ extern "C" int cls_place_pairs(cls_db* db, const cls_tree* t, const char* query1
         return fail(CLS_E_INTERNAL, std::string("cls_place_pairs: ") + ex.what());
     } catch (...) {
         return fail(CLS_E_INTERNAL, "cls_place_pairs: unknown exception");
+    }
+}
+
+// ---- read extraction use-case ------------------------------------------------------------------------------------------
+
+extern "C" int cls_extract_reads(cls_db* db, const cls_tree* t, const char* query1, const char* query2, int interleaved,
+                                 const uint64_t* include, uint32_t n_include, const uint64_t* exclude, uint32_t n_exclude, uint32_t select_flags,
+                                 const char* extract_path1, const char* extract_path2, const char* report_path, const char* summary_path,
+                                 const cls_params* params, const cls_fastq_opts* opts, uint32_t pair_flags, int overwrite, int all_rows,
+                                 uint64_t piece_bytes, cls_extract_totals* totals, uint32_t* n_placed, double* seconds) {
+    if (!db || !t || !query1 || !extract_path1) return fail(CLS_E_INVALID_ARG, "cls_extract_reads: null argument");
+    const bool pairs = query2 != nullptr || interleaved;
+    if (query2 && interleaved) return fail(CLS_E_INVALID_ARG, "cls_extract_reads: a mate file cannot be used with interleaved input");
+    if ((query2 != nullptr) != (extract_path2 != nullptr)) return fail(CLS_E_INVALID_ARG, "cls_extract_reads: a mate file and a second extract file go together");
+    if (!pairs && (summary_path || pair_flags)) return fail(CLS_E_INVALID_ARG, "cls_extract_reads: the pair options need paired input");
+    struct Guard {
+        FILE *f1 = nullptr, *f2 = nullptr;
+        cls_selector* sel = nullptr;
+        cls_pairer* pairer = nullptr;
+        cls_tally* tally = nullptr;
+        char *o1 = nullptr, *o2 = nullptr;
+        ~Guard() {
+            if (f1) fclose(f1);
+            if (f2) fclose(f2);
+            free(o1); free(o2);
+            cls_tally_destroy(tally);
+            cls_pairer_destroy(pairer);
+            cls_selector_destroy(sel);
+        }
+    } g;
+    try {
+        if (int rc = check_report_path(extract_path1, overwrite)) return rc;
+        if (extract_path2) if (int rc = check_report_path(extract_path2, overwrite)) return rc;
+        if (report_path) if (int rc = check_report_path(report_path, overwrite)) return rc;
+        if (summary_path) if (int rc = check_report_path(summary_path, overwrite)) return rc;
+        const auto t0 = std::chrono::steady_clock::now();
+        // (the selector first: an id that is no clade of the tree is refused before a file is touched)
+        int rc = cls_selector_create(db, include, n_include, exclude, n_exclude, select_flags, &g.sel);
+        if (rc != CLS_OK) return fail(rc, cls_last_error());
+        if (report_path && (rc = cls_tally_create(db, &g.tally)) != CLS_OK) return fail(rc, cls_last_error());
+        cls_extract_totals sum{};
+        uint64_t n = 0;
+        auto put = [&](FILE* f, const char* bytes, size_t len) { return len == 0 || fwrite(bytes, 1, len, f) == len; };
+        if (!pairs) {
+            std::string text;
+            if (strcmp(query1, "-") == 0) { std::stringstream ss; ss << std::cin.rdbuf(); text = ss.str(); }
+            else text = read_file(query1);
+            if (piece_bytes == 0) piece_bytes = DEFAULT_PIECE_BYTES;
+            const uint32_t max_pieces = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(MAX_PIECES, (text.size() + piece_bytes - 1) / piece_bytes));
+            std::vector<uint64_t> cuts((size_t)max_pieces + 1);
+            uint32_t n_pieces = 0;
+            if ((rc = cls_fastq_split(text.data(), text.size(), max_pieces, cuts.data(), &n_pieces)) != CLS_OK)
+                return fail(rc, "cls_extract_reads: cls_fastq_split failed");
+            g.f1 = fopen(extract_path1, "wb");
+            if (!g.f1) return fail(CLS_E_INVALID_ARG, std::string("Unable to open file ") + extract_path1);
+            for (uint32_t i = 0; i < n_pieces; ++i) {
+                size_t o_len = 0;
+                cls_extract_totals pt{};
+                uint32_t pn = 0, truncated = 0;
+                rc = cls_extract_fastq_text(db, g.sel, g.tally, text.data() + cuts[i], cuts[i + 1] - cuts[i], params, opts, &g.o1, &o_len, &pt, &pn,
+                                            &truncated);
+                if (rc != CLS_OK) return fail(rc, "cls_extract_reads: piece " + std::to_string(i) + ": " + cls_last_error());
+                if (!put(g.f1, g.o1, o_len)) return fail(CLS_E_INTERNAL, "Error writing to file");
+                free(g.o1);
+                g.o1 = nullptr;
+                n += pn;
+                sum.n_records += pt.n_records; sum.n_selected += pt.n_selected;
+                sum.n_selected_unplaced += pt.n_selected_unplaced; sum.bytes_out += pt.bytes_out;
+                if (truncated) break;  // (the pieces after the first one that stops early are dropped)
+            }
+            if (n >= (1ull << 32)) return fail(CLS_E_INVALID_ARG, "cls_extract_reads: more than 2^32 - 1 records");
+        } else {
+            const std::string text1 = read_file(query1), text2 = query2 ? read_file(query2) : std::string();
+            if ((rc = cls_pairer_create(db, &g.pairer)) != CLS_OK) return fail(rc, cls_last_error());
+            size_t l1 = 0, l2 = 0;
+            uint32_t pn = 0;
+            rc = cls_extract_fastq_pairs_text(db, g.pairer, g.sel, g.tally, text1.data(), text1.size(), query2 ? text2.data() : nullptr, text2.size(),
+                                              params, opts, pair_flags, &g.o1, &l1, &g.o2, &l2, &sum, &pn, nullptr);
+            if (rc != CLS_OK) return fail(rc, cls_last_error());
+            n = pn;
+            g.f1 = fopen(extract_path1, "wb");
+            if (!g.f1) return fail(CLS_E_INVALID_ARG, std::string("Unable to open file ") + extract_path1);
+            if (!put(g.f1, g.o1, l1)) return fail(CLS_E_INTERNAL, "Error writing to file");
+            if (extract_path2) {
+                g.f2 = fopen(extract_path2, "wb");
+                if (!g.f2) return fail(CLS_E_INVALID_ARG, std::string("Unable to open file ") + extract_path2);
+                if (!put(g.f2, g.o2, l2)) return fail(CLS_E_INTERNAL, "Error writing to file");
+            }
+        }
+        for (FILE** f : {&g.f1, &g.f2})
+            if (*f) {
+                const bool bad = fclose(*f) != 0;
+                *f = nullptr;
+                if (bad) return fail(CLS_E_INTERNAL, "Error writing to file");
+            }
+        if (report_path) {
+            std::vector<cls_tally_row> rows(t->rows.size(), cls_tally_row{});
+            cls_tally_totals tt{};
+            if ((rc = cls_tally_read(g.tally, rows.data(), (uint32_t)rows.size(), &tt)) != CLS_OK) return fail(rc, cls_last_error());
+            if ((rc = check_report_rows("cls_extract_reads", t, rows.data())) != CLS_OK) return rc;
+            if ((rc = write_report(t, rows.data(), &tt, all_rows, report_path)) != CLS_OK) return rc;
+        }
+        if (summary_path) if ((rc = write_pair_summary(g.pairer, summary_path)) != CLS_OK) return rc;
+        fprintf(stderr, "{\"code\":\"CLSEXTRACT0001\",\"%s\":%llu,\"selected\":%llu,\"selectedUnplaced\":%llu,\"bytesOut\":%llu}\n",
+                pairs ? "pairs" : "records", (unsigned long long)sum.n_records, (unsigned long long)sum.n_selected,
+                (unsigned long long)sum.n_selected_unplaced, (unsigned long long)sum.bytes_out);
+        if (totals) *totals = sum;
+        if (n_placed) *n_placed = (uint32_t)n;
+        if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return CLS_OK;
+    } catch (const std::exception& ex) {
+        return fail(CLS_E_INTERNAL, std::string("cls_extract_reads: ") + ex.what());
+    } catch (...) {
+        return fail(CLS_E_INTERNAL, "cls_extract_reads: unknown exception");
     }
 }

@@ -4,6 +4,9 @@
 //             [-i N] [-m COV] [-r] [-f] [--device N[,N...]] [--query-format fasta|fastq] [-q [5P,]3P]
 //             [--report PATH | --report-only PATH] [--report-all-clades]
 //             [-2 MATES | --interleaved] [--pair-mode deepest|conservative] [--pair-require-both] [--pair-summary PATH]
+//             [--extract-out FILE [--extract-out2 FILE] [--extract-clade ID[,ID...]] [--extract-exclude ID[,ID...]] [--extract-unplaced]]
+// --extract-out writes the FASTQ records of the reads (or pairs) placed where the --extract-... options say, instead of
+// per-read results (include/cls_host.h "read extraction").
 // -2 / --interleaved place paired-end FASTQ: one result per pair, under mate 1's header (include/cls_host.h).
 // --report also writes the per-clade abundance profile of the run (include/cls_host.h "clade report"); --report-only
 // writes nothing else: the reads are tallied on the device and no per-read output exists (-o is then not needed).
@@ -46,7 +49,13 @@ static void usage() {
             "      --pair-mode <deepest|conservative>  mates placed at a clade and at its ancestor: keep the deeper one, or\n"
             "                                      the ancestor [default: deepest]\n"
             "      --pair-require-both             leave a pair unplaced unless both mates are placed\n"
-            "      --pair-summary <PATH>           write the pair classes (tab-separated name, count)\n");
+            "      --pair-summary <PATH>           write the pair classes (tab-separated name, count)\n"
+            "      --extract-out <FILE>            fastq only: write the reads selected below, as they stand in QUERY, instead of\n"
+            "                                      per-read results (no -o); --report / --report-only still write the report\n"
+            "      --extract-out2 <FILE>           with -2: the second mates of the selected pairs\n"
+            "      --extract-clade <ID[,ID...]>    select the reads placed at or below these clades (Clade.id, decimal)\n"
+            "      --extract-exclude <ID[,ID...]>  but not those at or below these; the nearest listed clade above a read decides\n"
+            "      --extract-unplaced              select the reads that were not placed\n");
 }
 
 // cutadapt's -q: "3P" or "5P,3P", each a cutoff in 0 .. 2^31 - 1
@@ -63,6 +72,20 @@ static bool parse_cutoffs(const std::string& v, uint32_t* c5, uint32_t* c3) {
     return one(v.substr(0, comma), c5) && one(v.substr(comma + 1), c3);
 }
 
+// "ID[,ID...]": decimal Clade.id values
+static bool parse_ids(const std::string& v, std::vector<uint64_t>* ids) {
+    for (size_t p0 = 0; p0 <= v.size();) {
+        size_t p1 = v.find(',', p0);
+        if (p1 == std::string::npos) p1 = v.size();
+        const std::string x = v.substr(p0, p1 - p0);
+        if (x.empty() || x.size() > 20 || x.find_first_not_of("0123456789") != std::string::npos) return false;
+        if (x.size() == 20 && x > "18446744073709551615") return false;
+        ids->push_back(strtoull(x.c_str(), nullptr, 10));
+        p0 = p1 + 1;
+    }
+    return true;
+}
+
 int main(int argc, char** argv) {
     std::string query = "-", db_path, out_path, ann_path, fmt = "yaml";
     cls_params p;
@@ -73,6 +96,9 @@ int main(int argc, char** argv) {
     int all_rows = 0;
     std::string mate_file, pair_mode, pair_summary;
     bool interleaved = false, pair_require_both = false;
+    std::string extract_out, extract_out2;
+    std::vector<std::string> extract_clade, extract_exclude;
+    bool extract_unplaced = false;
     cls_fastq_opts fq;
     memset(&fq, 0, sizeof fq);
     for (int i = 1; i < argc; ++i) {
@@ -116,10 +142,32 @@ int main(int argc, char** argv) {
         else if (a == "--pair-mode") pair_mode = need("--pair-mode");
         else if (a == "--pair-require-both") pair_require_both = true;
         else if (a == "--pair-summary") pair_summary = need("--pair-summary");
+        else if (a == "--extract-out") extract_out = need("--extract-out");
+        else if (a == "--extract-out2") extract_out2 = need("--extract-out2");
+        else if (a == "--extract-clade") extract_clade.push_back(need("--extract-clade"));
+        else if (a == "--extract-exclude") extract_exclude.push_back(need("--extract-exclude"));
+        else if (a == "--extract-unplaced") extract_unplaced = true;
         else if (!a.empty() && a[0] == '-' && a != "-") { fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str()); usage(); return 2; }
         else query = a;
     }
-    if (db_path.empty() || (out_path.empty() && report_only.empty())) { usage(); return 2; }
+    const bool extract = !extract_out.empty();
+    if (!extract && (!extract_out2.empty() || !extract_clade.empty() || !extract_exclude.empty() || extract_unplaced)) {
+        fprintf(stderr, "error: the '--extract-...' options need '--extract-out'\n");
+        return 2;
+    }
+    std::vector<uint64_t> include_ids, exclude_ids;
+    if (extract) {
+        if (!out_path.empty()) { fprintf(stderr, "error: '--extract-out' cannot be used with '--output-file-path'\n"); return 2; }
+        if (qfmt != "fastq") { fprintf(stderr, "error: '--extract-out' needs '--query-format fastq'\n"); return 2; }
+        if (!devices.empty()) { fprintf(stderr, "error: reads are extracted on one device: '--device' takes one ordinal\n"); return 2; }
+        if (!extract_out2.empty() && mate_file.empty()) { fprintf(stderr, "error: '--extract-out2' needs '--mate-file'\n"); return 2; }
+        if (extract_out2.empty() && !mate_file.empty()) { fprintf(stderr, "error: '--mate-file' with '--extract-out' needs '--extract-out2'\n"); return 2; }
+        for (const auto& v : extract_clade)
+            if (!parse_ids(v, &include_ids)) { fprintf(stderr, "error: invalid value '%s' for '--extract-clade'\n", v.c_str()); return 2; }
+        for (const auto& v : extract_exclude)
+            if (!parse_ids(v, &exclude_ids)) { fprintf(stderr, "error: invalid value '%s' for '--extract-exclude'\n", v.c_str()); return 2; }
+    }
+    if (db_path.empty() || (out_path.empty() && report_only.empty() && !extract)) { usage(); return 2; }
     if (!report.empty() && !report_only.empty()) { fprintf(stderr, "error: '--report' cannot be used with '--report-only'\n"); return 2; }
     if (fmt != "yaml" && fmt != "jsonl") { fprintf(stderr, "error: invalid value '%s' for '--out-format'\n", fmt.c_str()); return 2; }
     if (qfmt != "fasta" && qfmt != "fastq") { fprintf(stderr, "error: invalid value '%s' for '--query-format'\n", qfmt.c_str()); return 2; }
@@ -167,7 +215,13 @@ int main(int argc, char** argv) {
     double seconds = 0;
     const int format = fmt == "yaml" ? CLS_FORMAT_YAML : CLS_FORMAT_JSONL;
     int rc;
-    if (pairs) {
+    if (extract) {
+        const std::string& rep = report_only.empty() ? report : report_only;
+        rc = cls_extract_reads(db, tree, query.c_str(), mate_file.empty() ? nullptr : mate_file.c_str(), interleaved ? 1 : 0, include_ids.data(),
+                               (uint32_t)include_ids.size(), exclude_ids.data(), (uint32_t)exclude_ids.size(), extract_unplaced ? CLS_SELECT_UNPLACED : 0u,
+                               extract_out.c_str(), extract_out2.empty() ? nullptr : extract_out2.c_str(), rep.empty() ? nullptr : rep.c_str(),
+                               pair_summary.empty() ? nullptr : pair_summary.c_str(), &p, &fq, pair_flags, overwrite, all_rows, 0, nullptr, &n, &seconds);
+    } else if (pairs) {
         const std::string& rep = report_only.empty() ? report : report_only;
         rc = cls_place_pairs(db, tree, query.c_str(), mate_file.empty() ? nullptr : mate_file.c_str(), report_only.empty() ? out_path.c_str() : nullptr,
                              rep.empty() ? nullptr : rep.c_str(), pair_summary.empty() ? nullptr : pair_summary.c_str(), &p, &fq, pair_flags, format,

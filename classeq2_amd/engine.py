@@ -32,13 +32,16 @@ EXPORTS = [
     "cls_tally_merge", "cls_tally_fasta_text", "cls_tally_fastq_text",
     "cls_pairer_create", "cls_pairer_destroy", "cls_pairer_totals", "cls_pair_records_device", "cls_pair_records", "cls_pair_host",
     "cls_pair_names_host", "cls_pair_names_device", "cls_place_fastq_pairs_text", "cls_tally_fastq_pairs_text",
+    "cls_selector_create", "cls_selector_destroy", "cls_select_records_device", "cls_select_records", "cls_select_host",
+    "cls_fastq_spans_device", "cls_extract_plan_device", "cls_extract_gather_device", "cls_extract_host", "cls_extract_fastq_text",
+    "cls_extract_fastq_pairs_text",
     "cls_version", "cls_set_tuning", "cls_tuning_from_env", "cls_kmers_build", "cls_kmers_desc", "cls_kmers_info_get", "cls_kmers_free",
 ]
 HOST_EXPORTS = [
     "cls_tree_load_json", "cls_tree_load", "cls_tree_init_from_file", "cls_tree_from_newick", "cls_tree_serialize", "cls_tree_save", "cls_tree_free", "cls_tree_set_annotations_yaml", "cls_tree_build_kmers_map", "cls_tree_build_kmers_map_device", "cls_tree_desc", "cls_serialize_results",
     "cls_host_free", "cls_place_sequences", "cls_place_sequences_group", "cls_place_sequences_ex", "cls_place_sequences_group_ex",
     "cls_host_last_error", "cls_tally_report", "cls_profile_sequences", "cls_profile_sequences_group", "cls_place_sequences_report", "cls_tree_nodes",
-    "cls_place_pairs",
+    "cls_place_pairs", "cls_extract_reads",
 ]
 SERVICE_EXPORTS = [
     "cls_service_create", "cls_service_destroy", "cls_service_add_model", "cls_service_submit", "cls_service_wait", "cls_service_pause",
@@ -159,6 +162,31 @@ def lib():
         L.cls_tally_fastq_pairs_text.argtypes = [vp, vp, vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params),
                                                  C.POINTER(_abi.FastqOpts), u32, C.POINTER(u32), C.POINTER(u32)]
         L.cls_tally_fastq_pairs_text.restype = i32
+        L.cls_selector_create.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(vp)]
+        L.cls_selector_create.restype = i32
+        L.cls_selector_destroy.argtypes = [vp]
+        L.cls_selector_destroy.restype = None
+        L.cls_select_records_device.argtypes = [vp, vp, u32, vp, vp]
+        L.cls_select_records_device.restype = i32
+        L.cls_select_records.argtypes = [vp, vp, u32, vp]
+        L.cls_select_records.restype = i32
+        L.cls_select_host.argtypes = [vp, u32, vp, u32, vp, u32, u32, vp, u64, vp]
+        L.cls_select_host.restype = i32
+        L.cls_fastq_spans_device.argtypes = [vp, u64, u32, vp, vp]
+        L.cls_fastq_spans_device.restype = i32
+        L.cls_extract_plan_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+        L.cls_extract_plan_device.restype = i32
+        L.cls_extract_gather_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+        L.cls_extract_gather_device.restype = i32
+        L.cls_extract_host.argtypes = [C.c_char_p, C.c_size_t, u32, vp, u64, C.POINTER(vp), C.POINTER(C.c_size_t), vp]
+        L.cls_extract_host.restype = i32
+        L.cls_extract_fastq_text.argtypes = [vp, vp, vp, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params), C.POINTER(_abi.FastqOpts), C.POINTER(vp),
+                                             C.POINTER(C.c_size_t), vp, C.POINTER(u32), C.POINTER(u32)]
+        L.cls_extract_fastq_text.restype = i32
+        L.cls_extract_fastq_pairs_text.argtypes = [vp, vp, vp, vp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(_abi.Params),
+                                                   C.POINTER(_abi.FastqOpts), u32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp),
+                                                   C.POINTER(C.c_size_t), vp, C.POINTER(u32), C.POINTER(u32)]
+        L.cls_extract_fastq_pairs_text.restype = i32
         L.cls_fasta_free.argtypes = [C.POINTER(_abi.Fasta)]
         L.cls_fasta_free.restype = None
         L.cls_last_error.restype = C.c_char_p
@@ -228,6 +256,10 @@ def lib():
         L.cls_place_pairs.argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(_abi.Params),
                                       C.POINTER(_abi.FastqOpts), u32, i32, i32, i32, C.POINTER(u32), C.POINTER(C.c_double)]
         L.cls_place_pairs.restype = i32
+        L.cls_extract_reads.argtypes = [vp, vp, C.c_char_p, C.c_char_p, i32, vp, u32, vp, u32, u32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                        C.POINTER(_abi.Params), C.POINTER(_abi.FastqOpts), u32, i32, i32, C.c_uint64, vp, C.POINTER(u32),
+                                        C.POINTER(C.c_double)]
+        L.cls_extract_reads.restype = i32
         # resident batching service (include/cls_service.h)
         L.cls_service_create.argtypes = [C.POINTER(vp)]
         L.cls_service_create.restype = i32
@@ -546,6 +578,41 @@ class PlacementDb:
                                                 pp, C.byref(o), flags, C.byref(n), C.byref(tr)))
         return n.value, bool(tr.value)
 
+    def extract_fastq_text(self, selector: "Selector", text: bytes, tally: Optional["Tally"] = None, params: Optional[_abi.Params] = None,
+                           trim_5p: int = 0, trim_3p: int = 0):
+        """FASTQ text -> (the selected records' bytes, totals: EXTRACT_TOTALS_DTYPE scalar, records placed, truncated): placed and
+        selected on the device, only the selected bytes return (cls_extract_fastq_text).  `tally` also receives the records."""
+        out, out_len = C.c_void_p(), C.c_size_t(0)
+        tot = np.zeros(1, dtype=_abi.EXTRACT_TOTALS_DTYPE)
+        n, tr = C.c_uint32(0), C.c_uint32(0)
+        pp = C.byref(params) if params is not None else None
+        o = _fastq_opts(trim_5p, trim_3p)
+        _check(lib().cls_extract_fastq_text(self._h, selector._h, tally._h if tally is not None else None, text, len(text), pp, C.byref(o),
+                                            C.byref(out), C.byref(out_len), tot.ctypes.data, C.byref(n), C.byref(tr)))
+        try:
+            return C.string_at(out, out_len.value), tot[0], n.value, bool(tr.value)
+        finally:
+            lib().cls_host_free(out)
+
+    def extract_fastq_pairs_text(self, pairer: "Pairer", selector: "Selector", text1: bytes, text2: Optional[bytes] = None,
+                                 tally: Optional["Tally"] = None, params: Optional[_abi.Params] = None, trim_5p: int = 0, trim_3p: int = 0,
+                                 flags: int = 0):
+        """Paired FASTQ text (`text2` None: interleaved) -> (out1, out2 or None, totals, pairs, truncated): the pair's record
+        decides for both mates (cls_extract_fastq_pairs_text)."""
+        o1, l1, o2, l2 = C.c_void_p(), C.c_size_t(0), C.c_void_p(), C.c_size_t(0)
+        tot = np.zeros(1, dtype=_abi.EXTRACT_TOTALS_DTYPE)
+        n, tr = C.c_uint32(0), C.c_uint32(0)
+        pp = C.byref(params) if params is not None else None
+        o = _fastq_opts(trim_5p, trim_3p)
+        _check(lib().cls_extract_fastq_pairs_text(self._h, pairer._h, selector._h, tally._h if tally is not None else None, text1, len(text1),
+                                                  text2, len(text2) if text2 is not None else 0, pp, C.byref(o), flags, C.byref(o1),
+                                                  C.byref(l1), C.byref(o2), C.byref(l2), tot.ctypes.data, C.byref(n), C.byref(tr)))
+        try:
+            return (C.string_at(o1, l1.value), C.string_at(o2, l2.value) if text2 is not None else None, tot[0], n.value, bool(tr.value))
+        finally:
+            lib().cls_host_free(o1)
+            lib().cls_host_free(o2)
+
     def set_max_read_len(self, n_bases: int) -> None:
         """Longest read place_batch_device() provisions for (cls_db_set_max_read_len)."""
         _check(lib().cls_db_set_max_read_len(self._h, n_bases))
@@ -668,6 +735,97 @@ class Pairer:
 
     def __exit__(self, *a):
         self.close()
+
+
+def _id_list(ids):
+    a = np.ascontiguousarray(np.asarray(list(ids) if ids is not None else [], dtype=np.uint64))
+    return a, (a.ctypes.data if len(a) else None), len(a)
+
+
+class Selector:
+    """A selection rule on the device of one PlacementDb (cls_selector): include / exclude clade ids, the nearest listed
+    clade on a record's path to the root decides; `unplaced` selects the records without a clade of the tree."""
+
+    def __init__(self, db: PlacementDb, include=(), exclude=(), unplaced: bool = False, flags: Optional[int] = None):
+        self._db = db  # (the selector borrows the handle)
+        self._h = C.c_void_p()
+        inc, pi, ni = _id_list(include)
+        exc, pe, ne = _id_list(exclude)
+        f = flags if flags is not None else (_abi.SELECT_UNPLACED if unplaced else 0)
+        _check(lib().cls_selector_create(db._h, pi, ni, pe, ne, f, C.byref(self._h)))
+
+    def select_device(self, d_records: int, n: int, d_sel: int, stream: int = 0) -> None:
+        """Device pointers in / out, asynchronous on `stream` (cls_select_records_device)."""
+        _check(lib().cls_select_records_device(self._h, d_records or None, n, d_sel or None, stream or None))
+
+    def select(self, records: np.ndarray) -> np.ndarray:
+        """Host records through the kernel (cls_select_records) -> one byte per record."""
+        recs = np.ascontiguousarray(records, dtype=_abi.PLACEMENT_DTYPE)
+        sel = np.full(len(recs), 0xFF, dtype=np.uint8)
+        _check(lib().cls_select_records(self._h, recs.ctypes.data, len(recs), sel.ctypes.data))
+        return sel
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().cls_selector_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def select_host(flat, records: np.ndarray, include=(), exclude=(), unplaced: bool = False, flags: Optional[int] = None) -> np.ndarray:
+    """The selection rule on the host, no device (cls_select_host) -> one byte per record."""
+    nodes = np.ascontiguousarray(flat.nodes, dtype=_abi.NODE_DTYPE)
+    recs = np.ascontiguousarray(records, dtype=_abi.PLACEMENT_DTYPE)
+    inc, pi, ni = _id_list(include)
+    exc, pe, ne = _id_list(exclude)
+    f = flags if flags is not None else (_abi.SELECT_UNPLACED if unplaced else 0)
+    sel = np.full(len(recs), 0xFF, dtype=np.uint8)
+    _check(lib().cls_select_host(nodes.ctypes.data, len(nodes), pi, ni, pe, ne, f, recs.ctypes.data, len(recs), sel.ctypes.data))
+    return sel
+
+
+def extract_host(text: bytes, sel: np.ndarray, stride: int = 1):
+    """Record text + output on the host, no device (cls_extract_host) -> (bytes, totals).  `sel`: one byte per item."""
+    sel = np.ascontiguousarray(sel, dtype=np.uint8)
+    out, out_len = C.c_void_p(), C.c_size_t(0)
+    tot = np.zeros(1, dtype=_abi.EXTRACT_TOTALS_DTYPE)
+    _check(lib().cls_extract_host(text, len(text), stride, sel.ctypes.data if len(sel) else None, len(sel), C.byref(out), C.byref(out_len),
+                                  tot.ctypes.data))
+    try:
+        return C.string_at(out, out_len.value), tot[0]
+    finally:
+        lib().cls_host_free(out)
+
+
+def fastq_spans_device(d_text: int, length: int, n: int, d_rec_off: int, stream: int = 0) -> None:
+    """rec_off[n + 1] of a FASTQ text in HBM (cls_fastq_spans_device)."""
+    _check(lib().cls_fastq_spans_device(d_text or None, length, n, d_rec_off or None, stream or None))
+
+
+def extract_plan_device(d_text: int, d_rec_off: int, stride: int, n_items: int, d_sel: int, d_out_off: int, stream: int = 0):
+    """The plan of the compaction on raw device pointers (cls_extract_plan_device) -> totals."""
+    tot = np.zeros(1, dtype=_abi.EXTRACT_TOTALS_DTYPE)
+    _check(lib().cls_extract_plan_device(d_text or None, d_rec_off or None, stride, n_items, d_sel or None, d_out_off or None, tot.ctypes.data,
+                                         stream or None))
+    return tot[0]
+
+
+def extract_gather_device(d_text: int, d_rec_off: int, stride: int, n_items: int, d_sel: int, d_out_off: int, d_out: int,
+                          stream: int = 0) -> None:
+    """The gather of the compaction on raw device pointers (cls_extract_gather_device); asynchronous on `stream`."""
+    _check(lib().cls_extract_gather_device(d_text or None, d_rec_off or None, stride, n_items, d_sel or None, d_out_off or None, d_out or None,
+                                           stream or None))
 
 
 def _pair_call(fn, a, b, flags, totals):
@@ -965,6 +1123,25 @@ def place_pairs(db: PlacementDb, tree: Tree, query1: str, query2: Optional[str] 
                                       C.byref(params) if params is not None else None, C.byref(o), flags, fmt, 1 if overwrite else 0,
                                       1 if all_rows else 0, C.byref(n), C.byref(sec)))
     return n.value, sec.value
+
+
+def extract_reads(db: PlacementDb, tree: Tree, query1: str, extract_path1: str, query2: Optional[str] = None, extract_path2: Optional[str] = None,
+                  interleaved: bool = False, include=(), exclude=(), unplaced: bool = False, report_path: Optional[str] = None,
+                  summary_path: Optional[str] = None, params: Optional[_abi.Params] = None, trim_quality=None, pair_flags: int = 0,
+                  overwrite: bool = False, all_rows: bool = False, piece_bytes: int = 0):
+    """The read-extraction use-case (cls_extract_reads): FASTQ file(s) -> the FASTQ records of the reads (or pairs) the
+    selector picks, plus the optional clade report / pair summary of the same pass -> (totals, records or pairs, seconds)."""
+    n, sec = C.c_uint32(0), C.c_double(0)
+    o = _fastq_opts(*_trim_pair(trim_quality))
+    enc = lambda x: x.encode() if x is not None else None
+    inc, pi, ni = _id_list(include)
+    exc, pe, ne = _id_list(exclude)
+    tot = np.zeros(1, dtype=_abi.EXTRACT_TOTALS_DTYPE)
+    _check_host(lib().cls_extract_reads(db._h, tree._h, query1.encode(), enc(query2), 1 if interleaved else 0, pi, ni, pe, ne,
+                                        _abi.SELECT_UNPLACED if unplaced else 0, extract_path1.encode(), enc(extract_path2), enc(report_path),
+                                        enc(summary_path), C.byref(params) if params is not None else None, C.byref(o), pair_flags,
+                                        1 if overwrite else 0, 1 if all_rows else 0, piece_bytes, tot.ctypes.data, C.byref(n), C.byref(sec)))
+    return tot[0], n.value, sec.value
 
 
 class Service:

@@ -152,6 +152,23 @@ int cls_place_pairs(cls_db* db, const cls_tree* t, const char* query1, const cha
                     const char* report_path, const char* summary_path, const cls_params* params, const cls_fastq_opts* opts,
                     uint32_t flags, int format, int overwrite, int all_rows, uint32_t* n_pairs, double* seconds);
 
+/* ---- read extraction use-case: FASTQ file(s) -> the FASTQ records of the reads placed where the selector says -------
+ * The selector (cls_place.h "read extraction") is `include` / `exclude` / `select_flags`.
+ * Single-end (`query2` NULL, `interleaved` 0; `query1` "-" = stdin): the query is cut with cls_fastq_split into pieces of
+ * about `piece_bytes` (0: 64 MiB) as cls_profile_sequences does, each piece goes through cls_extract_fastq_text with ONE
+ * selector (and one tally when `report_path` is given), each piece's output is appended to `extract_path1`, the pieces
+ * after the first truncated one are dropped: device and host memory are bounded by the piece.
+ * Paired (`query2` = the R2 file, or `interleaved`): whole files through cls_extract_fastq_pairs_text with `pair_flags`,
+ * as cls_place_pairs; with `query2`, `extract_path2` gets R2's records (both or neither); `summary_path` as there.
+ * `report_path` (may be NULL): the clade report of the same pass (of the pairs' records for paired input).  An existing
+ * file needs `overwrite`.  One JSON line of totals goes to stderr.  `totals`, `n_placed` (records, or pairs), `seconds`
+ * may be NULL. */
+int cls_extract_reads(cls_db* db, const cls_tree* t, const char* query1, const char* query2, int interleaved,
+                      const uint64_t* include, uint32_t n_include, const uint64_t* exclude, uint32_t n_exclude, uint32_t select_flags,
+                      const char* extract_path1, const char* extract_path2, const char* report_path, const char* summary_path,
+                      const cls_params* params, const cls_fastq_opts* opts, uint32_t pair_flags, int overwrite, int all_rows,
+                      uint64_t piece_bytes, cls_extract_totals* totals, uint32_t* n_placed, double* seconds);
+
 const char* cls_host_last_error(void);
 
 #ifdef __cplusplus

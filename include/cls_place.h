@@ -588,6 +588,86 @@ int cls_tally_fastq_pairs_text(cls_db* db, cls_pairer* p, cls_tally* tally, cons
                                size_t len2, const cls_params* params, const cls_fastq_opts* opts, uint32_t flags,
                                uint32_t* n_pairs, uint32_t* truncated);
 
+/* ---- read extraction: placement records -> the selected reads' original FASTQ text ------------------------------
+ * Selection.  A selector is a list of INCLUDE clade ids, a list of EXCLUDE clade ids and flags, against the tree of a
+ * handle.  A record is PLACED iff its status is CLS_IDENTITY_FOUND, CLS_MAX_RESOLUTION or CLS_INCONCLUSIVE and its
+ * clade_id is a clade of the tree (the pairing rule's "usable"); every other record is UNPLACED -- a status >= 12 and
+ * an unknown id included; none is an error.
+ *   - a placed record at clade v is selected iff the NEAREST listed clade on the path v -> root, v included, is an
+ *     include; with no listed clade on the path it is not selected.  So "include X, exclude Y below X, include Z below
+ *     Y" means what it reads.
+ *   - an unplaced record is selected iff CLS_SELECT_UNPLACED is set.
+ *   - CLS_E_INVALID_ARG: an id listed twice or in both lists, an id that is no clade of the tree, an unknown flag bit.
+ *     Empty lists are fine: no include + CLS_SELECT_UNPLACED is "the unplaced reads only"; include root + exclude X
+ *     is "everything placed outside X".
+ * Record text.  For the n records the FASTQ stage emits, record r is the bytes of lines 4r .. 4r+3 of the text as they
+ * are: '@', '+', the quality line and any '\r' stay, nothing is trimmed or filtered (quality trimming decides the
+ * placement, not the bytes written).  The spans are contiguous: record r = [rec_off[r], rec_off[r+1]), rec_off[r] = the
+ * start of line 4r, rec_off[n] = the start of line 4n, or `len` if the text ends inside line 4n-1.
+ * Items.  With `stride` s (1 or 2), item i covers [rec_off[i s], rec_off[(i+1) s]); s = 2 is an interleaved pair, both
+ * mates as they stand in the file.
+ * Output.  The bytes of the selected items in input order, concatenated; an item whose last byte is not '\n' gets one
+ * '\n' appended (only the last record of a text without a final newline); a zero-length item emits nothing.
+ * Totals per call, all 64-bit: n_records (items looked at), n_selected, n_selected_unplaced (the selected items whose
+ * record is unplaced; the plan and cls_extract_host see selection bytes, not records, and report 0), bytes_out. */
+typedef struct cls_selector cls_selector;      /* opaque; bound to one cls_db (a replica of a group included), lives on its device */
+#define CLS_SELECT_UNPLACED 1u
+typedef struct cls_extract_totals {
+    uint64_t n_records;
+    uint64_t n_selected;
+    uint64_t n_selected_unplaced;
+    uint64_t bytes_out;
+} cls_extract_totals;                          /* 32 bytes */
+
+/* A selector on the device of `db`.  It borrows the handle, like cls_tally: destroy it first.  Immutable: any number of
+ * launches may use it at once. */
+int cls_selector_create(cls_db* db, const uint64_t* include, uint32_t n_include, const uint64_t* exclude, uint32_t n_exclude,
+                        uint32_t flags, cls_selector** out);
+void cls_selector_destroy(cls_selector* s);
+/* `n` records in the HBM of the handle's device (8-byte aligned, as the tally takes them) -> one byte per record in
+ * `d_sel`: 1 selected, 0 not.  Asynchronous on `hip_stream`. */
+int cls_select_records_device(cls_selector* s, const void* d_records, uint32_t n, void* d_sel, void* hip_stream);
+/* Host buffers through the same kernel; synchronous. */
+int cls_select_records(cls_selector* s, const cls_placement* records, uint32_t n, uint8_t* sel);
+/* Host only, sequential, no device: the statement of the selection rule and the yardstick of the kernel.  The tree as
+ * cls_tally_host takes it. */
+int cls_select_host(const cls_node* nodes, uint32_t n_nodes, const uint64_t* include, uint32_t n_include,
+                    const uint64_t* exclude, uint32_t n_exclude, uint32_t flags,
+                    const cls_placement* records, uint64_t n, uint8_t* sel);
+
+/* rec_off[n + 1] (uint64) of the first n records of a FASTQ text in HBM (n = what cls_fastq_scan_device reported for
+ * it); the line structure alone decides, whatever the lines hold.  Synchronises `hip_stream`. */
+int cls_fastq_spans_device(const void* d_text, uint64_t len, uint32_t n, void* d_rec_off, void* hip_stream);
+
+/* The compaction in two steps, every buffer in the HBM of the current device, `d_sel` one byte per ITEM.
+ * plan: d_out_off[n_items + 1] (uint64) = the exclusive sum of the emitted lengths (0 for items that are not selected);
+ * synchronises `hip_stream` to return the sizes.  gather: copies; asynchronous; `d_out` holds totals->bytes_out bytes
+ * (any alignment) and must not alias the text; it writes those bytes and nothing else. */
+int cls_extract_plan_device(const void* d_text, const void* d_rec_off, uint32_t stride, uint32_t n_items, const void* d_sel,
+                            void* d_out_off, cls_extract_totals* totals, void* hip_stream);
+int cls_extract_gather_device(const void* d_text, const void* d_rec_off, uint32_t stride, uint32_t n_items, const void* d_sel,
+                              const void* d_out_off, void* d_out, void* hip_stream);
+/* Host only, sequential, no device: record text + items + output as stated above, from host text and one selection byte
+ * per item (it finds the lines itself; `n_items` = the emitted records / stride).  *out: malloc'ed, free() it. */
+int cls_extract_host(const char* text, size_t len, uint32_t stride, const uint8_t* sel, uint64_t n_items, char** out, size_t* out_len,
+                     cls_extract_totals* totals);
+
+/* Query text -> extracted text: the text goes to the device once (and stays there until the gather), the FASTQ stage,
+ * placement, the selection kernel on the records, plan + gather; only the selected bytes come back.  `tally` (may be
+ * NULL) receives the records on the device as in cls_tally_fastq_text.  *out: malloc'ed, free() it.  *n, *truncated as
+ * there (either may be NULL).  Synchronous. */
+int cls_extract_fastq_text(cls_db* db, cls_selector* s, cls_tally* tally, const char* text, size_t len, const cls_params* params,
+                           const cls_fastq_opts* opts, char** out, size_t* out_len, cls_extract_totals* totals,
+                           uint32_t* n, uint32_t* truncated);
+/* Pairs: the pair's record P (the pairing rule above with `flags`) decides for BOTH mates.  `text2` != NULL: *out1 /
+ * *out2 get R1's / R2's records of the selected pairs, in step.  `text2` == NULL (interleaved): *out1 gets both mates of
+ * each selected pair, *out2 stays NULL (`out2`, `out2_len` may be NULL).  The totals count pairs; bytes_out is the sum
+ * over both outputs.  `tally` (may be NULL) receives P.  Refusals as cls_place_fastq_pairs_text (CLS_E_BAD_PAIRS). */
+int cls_extract_fastq_pairs_text(cls_db* db, cls_pairer* p, cls_selector* s, cls_tally* tally, const char* text1, size_t len1,
+                                 const char* text2, size_t len2, const cls_params* params, const cls_fastq_opts* opts, uint32_t flags,
+                                 char** out1, size_t* out1_len, char** out2, size_t* out2_len, cls_extract_totals* totals,
+                                 uint32_t* n_pairs, uint32_t* truncated);
+
 /* Experiment knobs (grid sizes, locality-key definition, kernel family; none changes a result; names in
  * csrc/cls_tuning.h are the CLS_* variables in lower case without the prefix, e.g. "no_order").  Process-global,
  * meant for A/B runs: the library itself never reads the environment.  cls_tuning_from_env() takes every knob
